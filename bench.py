@@ -18,7 +18,12 @@ complete c~, G~, H~ (``--gather-root``: gather to rank 0 only) -- pycollo_amd/sh
 * ``--scaling weak``: ``--sections`` per GPU, the mesh grows with N; ``value`` is still evaluations of that (N times
   larger) NLP per second, and ``shard_evals_per_s`` = N x value is the per-shard rate.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and reports them; ``--full`` adds,
+each measured after the headline steps: the dominant kernel's `roofline` and `device_ms_per_step` (batches of their
+own behind a blocker), the host-pointer legs (`host`, `host_by_config`), the CPU port (`cpu_baseline`,
+`speedup_vs_cpu_port`) and, N > 1, `sharded_configs`.
+``--dump-outputs DIR`` writes c~, G~, H~ of the last timed step as DIR/{c,G,H}.npy (float64; a fixed seeded sample of
+each when together they exceed 64 MiB), for comparing two builds on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -42,6 +47,27 @@ def cpu_baseline(K_sections: int, order: int, budget_s: float = 21.0):
         return cport.time_hypersensitive(K_sections, order, budget_s)
     except Exception as exc:  # the baseline is reported, never required for the GPU number
         return {"value": None, "unit": "evals/s", "cores": 0, "kind": "port", "sample": f"unavailable: {exc}"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed: int = 0):
+    """Write each (name, fp64 device tensor) as out_dir/<name>.npy.  Above DUMP_LIMIT_BYTES in total every array keeps
+    the same share of its entries, at indices drawn (sorted) from a generator seeded by ``seed`` and the array's length
+    only, so two runs with the same arguments sample the same entries."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(8 * t.numel() for _, t in arrays)
+    keep = min(1.0, DUMP_LIMIT_BYTES / total) if total else 1.0
+    for name, t in arrays:
+        n = t.numel()
+        if keep < 1.0:
+            idx = np.sort(np.random.default_rng([seed, n]).choice(n, size=int(n * keep), replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+    return keep
 
 
 def host_leg(eng, x_np, lam_np, n_calls: int):
@@ -272,13 +298,18 @@ def main():
     ap.add_argument("--order", type=int, default=6, help="nodes per section")
     ap.add_argument("--problem", default="hypersensitive")
     ap.add_argument("--tpb", type=int, default=0, help="threads per block (0 = auto)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure the roofline / device time per step, the host-pointer "
+                         "legs, the CPU port baseline and (N > 1) the config-4 / config-5 sharded lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write c~, G~, H~ of the last timed step as DIR/<name>.npy (float64, at most 64 MiB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU port baseline")
     ap.add_argument("--build-only", action="store_true",
                     help="compile the code object this command needs and exit without touching the GPU (run this, "
                          "unprofiled, before any rocprofv3 pass: no compiler may be spawned under the profiler)")
-    ap.add_argument("--no-host", action="store_true", help="skip the host-pointer (pc_eval_all) timing leg")
-    ap.add_argument("--no-host-configs", action="store_true", help="skip the host-pointer lines of configs 3 and 4 (host_by_config)")
-    ap.add_argument("--host-calls", type=int, default=2000, help="timed host-pointer calls per variant (>= 1000)")
+    ap.add_argument("--no-host", action="store_true", help="--full: skip the host-pointer (pc_eval_all) timing leg")
+    ap.add_argument("--no-host-configs", action="store_true", help="--full: skip the host-pointer lines of configs 3 and 4 (host_by_config)")
+    ap.add_argument("--host-calls", type=int, default=2000, help="--full: timed host-pointer calls per variant (>= 1000)")
     ap.add_argument("--no-pin", action="store_true", help="leave the launching thread to the scheduler")
     ap.add_argument("--ragged", action="store_true", help="ph-refined style mesh: random section sizes, orders 4..8")
     ap.add_argument("--refined", type=int, default=0, metavar="NODES",
@@ -289,8 +320,10 @@ def main():
     ap.add_argument("--check", action="store_true", help="N > 1: compare the sharded result with an unsharded one")
     ap.add_argument("--overlap", action="store_true", help="N > 1: exchange the c / G runs while the H tiles still run (two tile launches)")
     ap.add_argument("--unpadded", action="store_true", help="N > 1: all-gatherv (one broadcast per rank at its exact length) instead of the padded all-gather")
-    ap.add_argument("--no-sharded-configs", action="store_true", help="N > 1: skip the config-4 / config-5 lines (BASELINE.json configs[3], configs[4])")
+    ap.add_argument("--no-sharded-configs", action="store_true", help="--full, N > 1: skip the config-4 / config-5 lines (BASELINE.json configs[3], configs[4])")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     if args.build_only:
@@ -486,10 +519,16 @@ def main():
         dt = float(tmax.item())
     evals_per_s = args.steps / dt   # evaluations of ONE NLP per second, whatever the number of ranks
 
+    # before anything else launches: the roofline's tile-only kernel writes into the same buffers
+    dump_keep = None
+    if args.dump_outputs and rank == 0:
+        dump_keep = dump_outputs(args.dump_outputs, [("c", c), ("G", G), ("H", H)] if world == 1 else
+                                 [("c", sh.c), ("G", sh.G), ("H", sh.H)])
+
     # ---- dominant kernel (bulk): K back-to-back launches between two HIP events on the launch stream
     roofline = None
     dev_step_ms = None
-    if bulk_only is not None:
+    if args.full:
         for _ in range(20):
             bulk_only()
         # The launches are queued behind a blocker (an fp64 GEMM of ~15 ms on the same stream) so that the GPU
@@ -554,7 +593,7 @@ def main():
 
     # ---- what a host-side caller (IPOPT) sees: pc_eval_all with host pointers in and out, one call at a time ----
     host = None
-    if world == 1 and not args.no_host:
+    if args.full and world == 1 and not args.no_host:
         # (eight timed loops of `calls` evaluations each: bounded to ~32 GB over the bus in total for large meshes; config 2 keeps its 2000)
         per_call = 8.0 * (eng.num_x + 2 * eng.num_c + eng.nnz_jac + eng.nnz_hess)
         calls = int(max(20, min(args.host_calls, 4e9 / per_call)))
@@ -563,7 +602,7 @@ def main():
     # (after every headline figure has been measured; a failure here -- the ranks are symmetric, so it is a failure on
     #  every rank -- is reported in the line instead of costing it)
     sharded_configs = None
-    if world > 1 and not args.no_sharded_configs:
+    if args.full and world > 1 and not args.no_sharded_configs:
         try:
             sharded_configs = sharded_config_lines(world, rank, local_rank, dev, tstream, args)
         except Exception as exc:   # noqa: BLE001
@@ -575,6 +614,8 @@ def main():
                "higher_is_better": True, "scaling": args.scaling if world > 1 else "strong", "vs_baseline": None, "dtype": "f64",
                "data": "synthetic",
                "config": {"workload": workload, **extra}}
+        if dump_keep is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "fraction_kept": round(dump_keep, 6)}
         if world > 1 and args.scaling == "weak":
             out["shard_evals_per_s"] = round(evals_per_s * world, 2)
         if sharded_configs is not None:
@@ -585,12 +626,12 @@ def main():
             out["host_ms_per_step"] = round(host["median_us"] * 1e-3, 6)
             out["host"] = host
         default_workload = args.problem == "hypersensitive" and args.sections == 2000 and args.order == 6 and not (args.ragged or args.refined or args.generic)
-        if world == 1 and not args.no_host and not args.no_host_configs and default_workload:
+        if args.full and world == 1 and not args.no_host and not args.no_host_configs and default_workload:
             if full_mask:
                 from pycollo_amd.hostpin import restore_affinity
                 restore_affinity(full_mask)
             out["host_by_config"] = host_by_config(local_rank, args.no_cpu)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             if full_mask:
                 from pycollo_amd.hostpin import restore_affinity
                 restore_affinity(full_mask)   # the CPU leg may use several cores

@@ -2,7 +2,7 @@
 # experiment lines: ENVV="VAR=.. VAR=.." label args...
 cd "$(dirname "$0")/.."
 out=${OUT:-gpurun_out/r4_exp.txt}
-run() { envv="$1"; label="$2"; shift 2; echo "== $label [$envv]: $*" >> $out; env $envv python bench.py --no-cpu --no-host --no-pin "$@" 2>>gpurun_out/r4_exp.err | python -c "
+run() { envv="$1"; label="$2"; shift 2; echo "== $label [$envv]: $*" >> $out; env $envv python bench.py --full --no-cpu --no-host --no-pin "$@" 2>>"${out%.txt}.err" | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

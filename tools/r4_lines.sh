@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 out=gpurun_out/r4_lines.txt
 : > $out
-run() { label="$1"; shift; env $ENVV python bench.py --no-cpu --no-host --no-pin "$@" 2>>gpurun_out/r4_lines.err | python -c "
+run() { label="$1"; shift; env $ENVV python bench.py --full --no-cpu --no-host --no-pin "$@" 2>>"${out%.txt}.err" | python -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()
