@@ -427,6 +427,60 @@ int pc_eval_resident(pc_handle* h, const double* x, double obj_factor, const dou
 /* device pointers of the results of the last evaluation that went through the handle's own buffers */
 int pc_device_results(pc_handle* h, const double** d_g, const double** d_jac, const double** d_hess);
 
+/* ---- derivative check of G~, grad J~ and H~ by coloured central differences ----------------------------------
+ * replaces: Iteration.check_nlp_functions (pycollo/iteration.py:455-458, which raises NotImplementedError when
+ * Settings.check_nlp_functions is on, pycollo/settings.py:360) -- IPOPT's derivative_test, which perturbs one column at a
+ * time (n + 1 evaluations), in coloured form: columns that share no row are perturbed together, and the number of colours
+ * does not grow with the mesh (csrc/pc_deriv.hpp documents the colouring).
+ *
+ * pc_deriv_plan works on a structure-only handle (device = -1) as well.  Every output may be NULL: the number of colours,
+ * the colour of every column [n], and per G~ entry [nnz_jac] 1 = located (its column is the only one of its colour in its
+ * row) / 0 = one term of the directional-derivative sum of (row, colour); per H~ entry [nnz_hess] bit 0 = located from
+ * its column's colour, bit 1 = from its row's colour (0: not located, the check refuses the model); per grad J~ non-zero
+ * 1 = located. */
+int pc_deriv_plan(const pc_handle* h, int32_t* n_colours, int32_t* colour, uint8_t* jac_flag, uint8_t* hess_flag,
+                  uint8_t* jgrad_flag);
+
+enum { PC_DERIV_JAC = 0, PC_DERIV_JAC_SUM = 1, PC_DERIV_HESS = 2, PC_DERIV_GRAD = 3 };
+#define PC_DERIV_MAX_REPORT 64
+typedef struct {
+  int32_t kind;         /* PC_DERIV_*: a located G~ entry, a sum (row, colour) of G~ entries, an H~ entry, a grad J~ non-zero */
+  int32_t located;      /* 1: (row, col) is the entry; 0 (PC_DERIV_JAC_SUM): col is the colour of the sum's columns */
+  int64_t index;        /* position in the kind's value array (G~, H~, grad J~ non-zeros) or number of the sum */
+  int64_t row, col;
+  double analytic, fd, err;   /* for a sum: sum_j an_j h_j and (c+_r - c-_r) / 2 */
+} pc_deriv_entry;
+typedef struct {
+  double tol;                 /* err > tol fails (0: 1e-4, IPOPT's derivative_test_tol) */
+  double delta;               /* h_j = delta max(1, |x~_j|) (0: 1e-5) */
+  int32_t max_report;         /* failing entries returned, <= PC_DERIV_MAX_REPORT */
+  int32_t reserved;
+  uint64_t seed;              /* lambda when d_lambda is NULL: uniform in [-1, 1] from this seed */
+  const double* d_jgrad_override;   /* device [n_jgrad] grad J~ non-zeros checked instead of the handle's (may be NULL) */
+  double* d_jac_fd;           /* device outputs (may be NULL): the FD estimate of every G~ entry (NaN for sum terms), */
+  double* d_hess_fd;          /* every H~ entry, */
+  double* d_jgrad_fd;         /* every grad J~ non-zero */
+} pc_deriv_opts;
+typedef struct {
+  int32_t ok;                 /* no entry above tol */
+  int32_t n_colours, n_evaluations, n_report;
+  double tol;
+  double max_err[3];          /* G~ (located and sums), H~, grad J~ */
+  pc_deriv_entry worst[3];    /* where each maximum occurs (lowest index on ties) */
+  int64_t n_fail[3];
+  int64_t n_jac_located, n_jac_sum_terms, n_sums, n_hess_located, n_jgrad_located;
+  pc_deriv_entry fail[PC_DERIV_MAX_REPORT];   /* the first max_report failures: G~ entries, sums, H~, grad J~, in entry order */
+} pc_deriv_report;
+/* Check the analytic G~ / H~ / grad J~ at d_x (device, scaled x~) against central differences of the handle's own c~, J~
+ * and grad L = sigma grad J~ + G~^T lambda, sigma = obj_factor, lambda = d_lambda (device [m]).  d_jac_override /
+ * d_hess_override (device, may be NULL) are checked in place of the handle's own values.  Queued on `stream` (NULL = the
+ * handle's), one host synchronisation at the end; reductions in a fixed order: the report is bit-reproducible.  Leaves the
+ * handle as it was (scaling, cached point of the new_x = 0 callbacks, pc_device_results, tile partial sums).  A handle
+ * restricted by pc_set_tile_range (or with a caller-owned partials buffer) is refused. */
+int pc_check_derivatives_device(pc_handle* h, const double* d_x, double obj_factor, const double* d_lambda,
+                                const double* d_jac_override, const double* d_hess_override, const pc_deriv_opts* opts,
+                                pc_deriv_report* report, void* stream);
+
 /* timing of the last n pc_eval_all_device launches is measured by the caller with HIP events on the
  * stream it passed; this returns the stream the handle owns (hipStream_t) */
 void* pc_stream(pc_handle* h);

@@ -17,7 +17,9 @@
 #include "pc_args.h"
 #include "pc_pattern.hpp"
 #include "pc_desc.hpp"
+#include "pc_deriv.hpp"
 
+struct pc_deriv_dev;   // (pc_deriv_check.hpp: the derivative check's device buffers)
 struct pc_kkt;   // (pc_kkt.hip; the interior-point state below drives it through the exported calls)
 
 namespace {
@@ -214,6 +216,9 @@ struct pc_handle {
   int n_launches = 0;
   int lds_max = 0;
   int lds_limit = 64 * 1024;  // dynamic LDS a workgroup may request (queried from the device)
+  // derivative check (pc_deriv.hpp, pc_deriv_check.hpp): colouring plan and scratch, built on first use
+  mutable std::shared_ptr<pcd::Plan> deriv_plan;
+  std::shared_ptr<pc_deriv_dev> deriv_dev;
 };
 
 namespace {
@@ -1770,3 +1775,4 @@ int pc_read_symbol(pc_handle* h, const char* name, void* dst, size_t bytes) {
 }  // extern "C"
 
 #include "pc_ipm.hpp"   // the device-resident interior-point state (same translation unit: it uses launch_all)
+#include "pc_deriv_check.hpp"   // the derivative check (same translation unit: it uses launch_all)

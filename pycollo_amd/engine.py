@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 
 import numpy as np
 import scipy.sparse as sparse
@@ -66,6 +67,99 @@ class _Info(C.Structure):
                 ("algorithmic_bytes", C.c_int64), ("n_tiles_total", C.c_int32), ("threads_per_block", C.c_int32),
                 ("lds_bytes_max", C.c_int32), ("n_launches", C.c_int32), ("waves_per_tile", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class _DerivEntry(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("located", C.c_int32), ("index", C.c_int64), ("row", C.c_int64), ("col", C.c_int64),
+                ("analytic", C.c_double), ("fd", C.c_double), ("err", C.c_double)]
+
+
+PC_DERIV_MAX_REPORT = 64
+
+
+class _DerivOpts(C.Structure):
+    _fields_ = [("tol", C.c_double), ("delta", C.c_double), ("max_report", C.c_int32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("d_jgrad_override", C.c_void_p), ("d_jac_fd", C.c_void_p),
+                ("d_hess_fd", C.c_void_p), ("d_jgrad_fd", C.c_void_p)]
+
+
+class _DerivReport(C.Structure):
+    _fields_ = [("ok", C.c_int32), ("n_colours", C.c_int32), ("n_evaluations", C.c_int32), ("n_report", C.c_int32),
+                ("tol", C.c_double), ("max_err", C.c_double * 3), ("worst", _DerivEntry * 3), ("n_fail", C.c_int64 * 3),
+                ("n_jac_located", C.c_int64), ("n_jac_sum_terms", C.c_int64), ("n_sums", C.c_int64),
+                ("n_hess_located", C.c_int64), ("n_jgrad_located", C.c_int64),
+                ("fail", _DerivEntry * PC_DERIV_MAX_REPORT)]
+
+
+_DERIV_KIND = ("jac", "jac_sum", "hess", "grad")
+
+
+@dataclass(frozen=True)
+class DerivEntry:
+    """One entry of a derivative check.  ``kind``: "jac" (G~ entry), "jac_sum" (a sum of G~ entries over the columns of
+    one colour in one row: ``col`` is the colour, ``analytic`` = sum an_j h_j, ``fd`` = (c+ - c-) / 2), "hess" (H~ entry),
+    "grad" (grad J~ non-zero; ``row`` = -1).  ``index``: position in the kind's value array (or number of the sum)."""
+    kind: str
+    row: int
+    col: int
+    analytic: float
+    fd: float
+    err: float
+    located: bool
+    index: int
+
+    @staticmethod
+    def _of(e):
+        return DerivEntry(_DERIV_KIND[e.kind], int(e.row), int(e.col), float(e.analytic), float(e.fd), float(e.err),
+                          bool(e.located), int(e.index))
+
+
+@dataclass
+class DerivativeCheck:
+    """What ``pc_check_derivatives_device`` reports (include/pycollo_amd.h, pc_deriv_report): err = |an - fd| / max(1, |an|)
+    per located entry, the largest term of the sum for a sum; ``ok`` when no entry exceeds ``tol``."""
+    ok: bool
+    tol: float
+    max_err_jac: float
+    max_err_hess: float
+    max_err_grad: float
+    worst_jac: DerivEntry | None
+    worst_hess: DerivEntry | None
+    worst_grad: DerivEntry | None
+    n_fail_jac: int
+    n_fail_hess: int
+    n_fail_grad: int
+    failures: list
+    n_colours: int
+    n_evaluations: int
+    n_jac_located: int
+    n_jac_sum_terms: int
+    n_sums: int
+    n_hess_located: int
+    n_jgrad_located: int
+    jac_fd: np.ndarray | None = None
+    hess_fd: np.ndarray | None = None
+    jgrad_fd: np.ndarray | None = None
+
+    @property
+    def n_fail(self) -> int:
+        return self.n_fail_jac + self.n_fail_hess + self.n_fail_grad
+
+    @property
+    def max_err(self) -> float:
+        return max(self.max_err_jac, self.max_err_hess, self.max_err_grad)
+
+
+@dataclass
+class DerivativePlan:
+    """The colouring of the derivative check (``pc_deriv_plan``): colour of every column of x~; per G~ entry located
+    (else a term of the sum of its (row, colour)); per H~ entry bit 0 = located from its column's colour, bit 1 = from its
+    row's; per grad J~ non-zero located."""
+    n_colours: int
+    colour: np.ndarray
+    jac_located: np.ndarray
+    hess_flag: np.ndarray
+    jgrad_located: np.ndarray
 
 
 _lib = None
@@ -123,6 +217,9 @@ def load_library() -> C.CDLL:
     lib.pc_copy_runs.argtypes = [vp, vp, vp, C.c_int64, vp]
     lib.pc_run_chunk.argtypes = []
     lib.pc_mesh_error.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.pc_deriv_plan.argtypes = [vp, _i32p, vp, vp, vp, vp]
+    lib.pc_check_derivatives_device.argtypes = [vp, vp, C.c_double, vp, vp, vp, C.POINTER(_DerivOpts),
+                                                C.POINTER(_DerivReport), vp]
     lib.pc_stream.argtypes = [vp]
     lib.pc_stream.restype = vp
     _lib = lib
@@ -595,6 +692,73 @@ class NlpEngine:
         self._check(self._lib.pc_mesh_error(self._h, phase, x.ctypes.data, len(od), od.ctypes.data, B.ctypes.data,
                                             E.ctypes.data, A.ctypes.data, rel.ctypes.data, ab.ctypes.data))
         return rel, ab[:, :n_y]
+
+    # ---- derivative check (pycollo/iteration.py:455-458, pycollo/settings.py:360) ----------------------------
+    def derivative_plan(self) -> DerivativePlan:
+        """The colouring the derivative check perturbs by (``pc_deriv_plan``); works on a structure-only engine."""
+        nc = C.c_int32()
+        colour = np.empty(self.num_x, dtype=np.int32)
+        jl = np.empty(self.nnz_jac, dtype=np.uint8)
+        hf = np.empty(self.nnz_hess, dtype=np.uint8)
+        jg = np.empty(len(self.model.point.J_grad), dtype=np.uint8)
+        self._check(self._lib.pc_deriv_plan(self._h, C.byref(nc), colour.ctypes.data, jl.ctypes.data, hf.ctypes.data,
+                                            jg.ctypes.data))
+        return DerivativePlan(int(nc.value), colour, jl.astype(bool), hf, jg.astype(bool))
+
+    def jgrad_columns(self) -> np.ndarray:
+        """x index of every structural non-zero of grad J~ (the order of ``jgrad_values`` and ``jgrad_fd``)."""
+        return self.layout.point_x_index()[np.array([c for c, _ in self.model.point.J_grad], dtype=np.int64)]
+
+    def check_derivatives(self, x, obj_factor=1.0, lagrange=None, *, tol=1e-4, delta=1e-5, jac_values=None, hess_values=None,
+                          jgrad_values=None, max_report=20, seed=0, return_fd=False) -> DerivativeCheck:
+        """IPOPT's ``derivative_test`` for this NLP, in coloured form: G~, grad J~ and H~ of sigma J~ + lambda . c~ at the
+        scaled point ``x`` against central differences of c~, J~ and grad L (``pc_check_derivatives_device``).  ``x`` /
+        ``lagrange`` / the value arrays may be NumPy arrays or device tensors; ``lagrange=None``: lambda uniform in
+        [-1, 1] from ``seed``.  ``jac_values`` / ``hess_values`` / ``jgrad_values``: values checked in place of the
+        engine's own (CSR order as ``evaluate_*_nonzeros``; grad J~ as its structural non-zeros).  ``tol`` = 1e-4 is
+        IPOPT's ``derivative_test_tol``.  The engine is left as it was: cached point, device results, scaling."""
+        import torch
+        if self.device < 0:
+            raise RuntimeError("check_derivatives needs a GPU engine (device=None builds the structure only)")
+        dev = torch.device("cuda", self.device)
+
+        def on_dev(a, size, name):
+            if a is None:
+                return None
+            t = torch.as_tensor(a, dtype=torch.float64, device=dev).reshape(-1).contiguous()
+            if t.numel() != size:
+                raise ValueError(f"{name} must have {size} entries")
+            return t
+
+        n_jg = len(self.model.point.J_grad)
+        dx = on_dev(x, self.num_x, "x")
+        dl = on_dev(lagrange, self.num_c, "lagrange")
+        dG = on_dev(jac_values, self.nnz_jac, "jac_values")
+        dH = on_dev(hess_values, self.nnz_hess, "hess_values")
+        dJ = on_dev(jgrad_values, n_jg, "jgrad_values")
+        fd = [torch.empty(k, dtype=torch.float64, device=dev) for k in (self.nnz_jac, self.nnz_hess, n_jg)] if return_fd else None
+        opts = _DerivOpts(tol=float(tol), delta=float(delta), max_report=int(min(max_report, PC_DERIV_MAX_REPORT)),
+                          seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        opts.d_jgrad_override = ptr(dJ)
+        if fd is not None:
+            opts.d_jac_fd, opts.d_hess_fd, opts.d_jgrad_fd = (ptr(t) if t.numel() else None for t in fd)
+        rep = _DerivReport()
+        torch.cuda.synchronize(dev)   # (the inputs were written on torch's stream; the check runs on the handle's)
+        self._check(self._lib.pc_check_derivatives_device(self._h, ptr(dx), float(obj_factor), ptr(dl), ptr(dG), ptr(dH),
+                                                          C.byref(opts), C.byref(rep), None))
+        worst = [DerivEntry._of(e) if e.kind >= 0 else None for e in rep.worst]
+        out = DerivativeCheck(
+            ok=bool(rep.ok), tol=float(rep.tol), max_err_jac=float(rep.max_err[0]), max_err_hess=float(rep.max_err[1]),
+            max_err_grad=float(rep.max_err[2]), worst_jac=worst[0], worst_hess=worst[1], worst_grad=worst[2],
+            n_fail_jac=int(rep.n_fail[0]), n_fail_hess=int(rep.n_fail[1]), n_fail_grad=int(rep.n_fail[2]),
+            failures=[DerivEntry._of(rep.fail[i]) for i in range(rep.n_report)], n_colours=int(rep.n_colours),
+            n_evaluations=int(rep.n_evaluations), n_jac_located=int(rep.n_jac_located),
+            n_jac_sum_terms=int(rep.n_jac_sum_terms), n_sums=int(rep.n_sums), n_hess_located=int(rep.n_hess_located),
+            n_jgrad_located=int(rep.n_jgrad_located))
+        if fd is not None:
+            out.jac_fd, out.hess_fd, out.jgrad_fd = (t.cpu().numpy() for t in fd)
+        return out
 
     def synchronize(self):
         self._check(self._lib.pc_synchronize(self._h))

@@ -188,6 +188,7 @@ class Mi355x:
         self.problem_obj: PycolloGpuProblem | None = None
         self.current_iteration = None
         self._spec = None
+        self.derivative_check = None
 
     # ---- per mesh iteration (backend.py:1403-1411) ------------------------------------------------
     def generate_nlp_function_callables(self, iteration):
@@ -261,6 +262,24 @@ class Mi355x:
         return {"x": np.asarray(x), "f": float(info["obj_val"]), "g": np.asarray(info["g"]), "lam_g": np.asarray(info["mult_g"]),
                 "lam_x": np.asarray(info["mult_x_U"]) - np.asarray(info["mult_x_L"]), "status": info["status"],
                 "status_msg": info["status_msg"]}
+
+    def check_nlp_functions(self):
+        """What pycollo's ``Iteration.check_nlp_functions`` (pycollo/iteration.py:455-458, NotImplementedError there) routes
+        to when ``settings.check_nlp_functions`` is on (pycollo/settings.py:360): G~, grad J~ and H~ at the iteration's
+        scaled guess against coloured central differences (``NlpEngine.check_derivatives``).  The report is kept in
+        ``self.derivative_check`` (None with the setting off); a failed check warns and does not raise."""
+        self.derivative_check = None
+        if not getattr(self.ocp.settings, "check_nlp_functions", False):
+            return None
+        if self.problem_obj is None:
+            self.create_nlp_solver()   # (the iteration's scaling)
+        check = self.engine.check_derivatives(np.asarray(self.current_iteration.guess_x, float))
+        if not check.ok:
+            import warnings
+            warnings.warn(f"derivative check failed: {check.n_fail} entries above tol {check.tol:g} (largest error "
+                          f"{check.max_err:.3e})", RuntimeWarning, stacklevel=2)
+        self.derivative_check = check
+        return check
 
     def solve_nlp(self):
         it = self.current_iteration

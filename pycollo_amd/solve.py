@@ -23,7 +23,7 @@ class OcpResult:
     objective: float
     mesh_tolerance_met: bool
     mesh_iterations: int
-    iterations: list = field(default_factory=list)   # per mesh iteration: dict(K, N, objective, status, nlp_iterations, max_rel_err)
+    iterations: list = field(default_factory=list)   # per mesh iteration: dict(K, N, objective, status, nlp_iterations, max_rel_err[, derivative_check])
     final: MeshIteration | None = None
     gpu_linear_solver_gave_up: list = field(default_factory=list)   # mesh iterations whose NLP was repeated with the host factorisation
     # mesh iterations whose NLP ended "acceptable" because a line search failed at a point already inside the acceptable
@@ -34,14 +34,18 @@ class OcpResult:
 def solve_ocp(problem, *, max_mesh_iterations: int = 10, mesh_tolerance: float = MESH_TOLERANCE, device: int = 0,
               nlp_tol: float = 1e-10, nlp_max_iter: int = 2000, verbose: int = 0, update_scaling: bool = False,
               scaling_weight: float = 0.8, linear_solver: str = "resident", warm_start: bool = False,
-              host_retry: bool = False) -> OcpResult:
+              host_retry: bool = False, check_nlp_functions: bool = False) -> OcpResult:
     """Solve ``problem`` (a :class:`pycollo_amd.problem.ProblemSpec`) on its initial mesh, refine, repeat.
     ``nlp_tol`` / ``nlp_max_iter``: the reference's defaults (pycollo/settings.py:60-61: 1e-10, 2000) -- with 1e-8 the tumour
     problem stops 2e-7 short of its mesh tolerance after ten mesh iterations, with 1e-10 it meets it as the reference does;
     ``update_scaling`` / ``scaling_weight``: pycollo/settings.py:272-296 (scalings averaged over the mesh iterations);
     ``warm_start``: pycollo/settings.py:228 (IPOPT's ``warm_start_init_point``, every mesh iteration);
     ``host_retry``: repeat a GPU-factorised NLP solve that did not succeed with the host factorisation (off: a failed
-    solve ends the loop and the result says so)."""
+    solve ends the loop and the result says so);
+    ``check_nlp_functions``: pycollo/settings.py:360 -- before every NLP solve, G~, grad J~ and H~ are checked against
+    coloured central differences at the mesh iteration's scaled initial guess (``NlpEngine.check_derivatives``, where the
+    reference's Iteration.__init__ calls its unimplemented check, pycollo/iteration.py:78,455-458); the report goes to
+    ``iterations[k]["derivative_check"]``, a failed check warns (RuntimeWarning) and the solve goes on."""
     import os
     linear_solver = os.environ.get("PYCOLLO_AMD_LINEAR_SOLVER", linear_solver)   # (A/B knob: "gpu" | "resident" | "host")
     prob = copy.deepcopy(problem)
@@ -56,6 +60,13 @@ def solve_ocp(problem, *, max_mesh_iterations: int = 10, mesh_tolerance: float =
         it = MeshIteration(prob, device=device, prev=prev, number=k + 1, update_scaling=update_scaling,
                            scaling_weight=scaling_weight, history=history)
         history.append(it.scaling_record)
+        check = None
+        if check_nlp_functions:
+            check = it.engine.check_derivatives(it.guess_x_tilde)
+            if not check.ok:
+                import warnings
+                warnings.warn(f"mesh iteration {k + 1}: the derivative check failed ({check.n_fail} entries above tol "
+                              f"{check.tol:g}; largest error {check.max_err:.3e})", RuntimeWarning, stacklevel=2)
         res = it.solve_with_ipm(max_iter=nlp_max_iter, tol=nlp_tol, verbose=max(0, verbose - 1), linear_solver=linear_solver,
                                 warm_start=warm_start, host_retry=host_retry)
         errs = mesh_error(it.engine, it.x_tilde)
@@ -63,6 +74,8 @@ def solve_ocp(problem, *, max_mesh_iterations: int = 10, mesh_tolerance: float =
         log.append({"K": [int(m.K) for m in it.meshes], "N": [int(pl.N) for pl in it.layout.phases],
                     "objective": float(it.objective), "status": res.status, "nlp_iterations": int(res.iterations),
                     "max_rel_err": worst, "seconds": float(res.seconds), "evaluations": dict(res.evaluations)})
+        if check is not None:
+            log[-1]["derivative_check"] = check
         if "gpu_linear_solver_gave_up" in res.evaluations:
             gave_up.append(k + 1)
         if res.evaluations.get("acceptable_after_failed_line_search"):
