@@ -8,7 +8,7 @@ of :class:`pycollo_amd.engine.PycolloGpuProblem` -- so the end-to-end ``solve()`
 integration tests can be used as tests of the GPU path.
 
 Algorithm: the line-search filter interior-point method of Waechter & Biegler (Math. Program. 106, 2006), the
-method IPOPT implements, without its restoration phase and second-order correction:
+method IPOPT implements, with its second-order correction and a Gauss-Newton stand-in for its restoration phase:
 
   min f(x)  s.t.  c_E(x) = c_E^L,  c_I^L <= c_I(x) <= c_I^U,  x^L <= x <= x^U
   ->  slacks s for the inequality rows;  barrier  phi_mu = f - mu sum log(v - v^L) - mu sum log(v^U - v);
@@ -16,16 +16,26 @@ method IPOPT implements, without its restoration phase and second-order correcti
   inertia-free regularisation (curvature test on the step), fraction-to-the-boundary rule, filter on
   (constraint violation, barrier objective), monotone mu update.
 
-The linear algebra goes through four methods (``_JT``, ``_solve_kkt``, ``_ls_multipliers``, ``_gn_step``).
-:class:`InteriorPointSolver` implements them on the host with SuperLU (``scipy.sparse.linalg.splu``) on matrices the
-callbacks delivered as host arrays; :class:`GpuInteriorPointSolver` (row N4) implements them with the block L D L^T
-of ``pycollo_amd.kkt`` on G~ / H~ that never leave device memory -- only vectors cross the bus.
+There is one loop, :meth:`InteriorPointSolver.solve`, and it handles scalars only.  It asks an iterate for them through
+the steps the C interface names (``pc_ipm_*``, include/pycollo_amd.h): ``_set_state`` / ``_get_state``, ``_eval_point``,
+``_errors``, ``_newton``, ``_trial``, ``_soc`` / ``_soc_restore``, ``_accept``; only its rare restoration branch works
+on vectors, which it gets and hands back through the first three.  Two layers can be swapped under it:
+
+* the steps: :class:`InteriorPointSolver` keeps the vectors on the host (``self.st``) and builds the steps from the
+  callbacks and five linear-algebra methods (``_JT``, ``_solve_kkt``, ``_resolve_kkt``, ``_ls_multipliers``, ``_gn_step``);
+  :class:`ResidentInteriorPointSolver` keeps the vectors in device memory and every step is one C call;
+* the linear algebra under the host-vector steps: SuperLU (``scipy.sparse.linalg.splu``) on matrices the callbacks
+  delivered as host arrays in :class:`InteriorPointSolver`; the block L D L^T of ``pycollo_amd.kkt`` on G~ / H~ that never
+  leave device memory in :class:`GpuInteriorPointSolver` (row N4; ``ipm_sharded`` cuts the same across ranks).
+
 Multiplier sign convention: L = obj_factor f + lambda^T c, as IPOPT's ``eval_h`` expects.
 """
 from __future__ import annotations
 
+import ctypes as C
 import time
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 
 import numpy as np
 import scipy.sparse as sp
@@ -56,6 +66,8 @@ class IpmResult:
 
 
 class InteriorPointSolver:
+    """The loop (:meth:`solve`), and its steps on host vectors with SuperLU under them."""
+
     def __init__(self, problem_obj, n: int, m: int, lb, ub, cl, cu, tol: float = 1e-8, acceptable_tol: float = 1e-6,
                  max_iter: int = 300, mu_init: float = 0.1, verbose: int = 0, warm_start: bool = False,
                  gradient_scaling: bool = True, second_order_correction: bool = True):
@@ -268,10 +280,130 @@ class InteriorPointSolver:
         dr[self.free] = sol[:self.nf]
         return dr
 
+    # ---- the steps of an iteration ----------------------------------------------------------------
+    # What the loop asks of an iterate: scalars out, the vectors stay where they are -- here in ``self.st`` on the host,
+    # in ResidentInteriorPointSolver behind the pc_ipm_* call of the same name (include/pycollo_amd.h).
+    def _set_state(self, v, lam, zl, zu):
+        s = self.st
+        s.v, s.lam, s.zl, s.zu = v, lam, zl, zu
+
+    def _get_state(self):
+        s = self.st
+        return s.v, s.lam, s.zl, s.zu, s.c, s.g
+
+    def _eval_point(self):
+        """Scaled f and sum |c| at the current v (grad f and J there are ``_start_at``'s)."""
+        s = self.st
+        s.f, s.c = self._f(s.v[:self.n]), self._c(s.v)
+        return s.f, float(np.sum(np.abs(s.c)))
+
+    def _errors(self):
+        """max |grad L| over the free unknowns, max |c|, sum |c|, max / min of (v - vl) zl, max / min of (vu - v) zu,
+        sum |lambda|, sum zl, sum zu: E_mu of Waechter & Biegler eq. (5) follows for any mu."""
+        s, e = self.st, np.zeros(10)
+        s.JTlam = self._JT(s.J, s.lam)
+        if self.nf:
+            e[0] = np.max(np.abs((s.g + s.JTlam - s.zl + s.zu)[self.free]))
+        if self.m:
+            e[1] = np.max(np.abs(s.c))
+        e[2] = np.sum(np.abs(s.c))
+        with np.errstate(invalid="ignore"):   # (inf x 0 where there is no bound: masked out)
+            if self.hasl.any():
+                comp = ((s.v - self.vl) * s.zl)[self.hasl]
+                e[3], e[4] = np.max(comp), np.min(comp)
+            if self.hasu.any():
+                comp = ((self.vu - s.v) * s.zu)[self.hasu]
+                e[5], e[6] = np.max(comp), np.min(comp)
+        e[7], e[8], e[9] = np.sum(np.abs(s.lam)), np.sum(s.zl), np.sum(s.zu)
+        return e
+
+    def _bound_steps(self, mu, tau):
+        """The bound multipliers' steps that go with the step ``st.dv``; its fraction-to-the-boundary limits alpha_max, alpha_z."""
+        s = self.st
+        s.dzl = np.where(self.hasl, mu / s.dlv - s.zl - s.zl / s.dlv * s.dv, 0.0)
+        s.dzu = np.where(self.hasu, mu / s.duv - s.zu + s.zu / s.duv * s.dv, 0.0)
+        a_z = min(self._alpha_dual(s.zl[self.hasl], s.dzl[self.hasl], tau) if self.hasl.any() else 1.0,
+                  self._alpha_dual(s.zu[self.hasu], s.dzu[self.hasu], tau) if self.hasu.any() else 1.0)
+        return self._alpha_max(s.v, s.dv, tau), a_z
+
+    def _newton(self, mu, tau, dw_last):
+        """The Newton step for barrier parameter mu (after ``_errors`` at this point): dw (negative: the regularisation
+        failed), alpha_max, alpha_z, grad phi . dv, mu x barrier sum at v."""
+        s = self.st
+        s.dlv, s.duv = np.where(self.hasl, s.v - self.vl, 1.0), np.where(self.hasu, self.vu - s.v, 1.0)
+        Sigma = np.where(self.hasl, s.zl / s.dlv, 0.0) + np.where(self.hasu, s.zu / s.duv, 0.0)
+        W = self._W(s.v[:self.n], s.lam)
+        s.grad_phi = s.g - np.where(self.hasl, mu / s.dlv, 0.0) + np.where(self.hasu, mu / s.duv, 0.0)
+        t_kkt = time.perf_counter()
+        try:
+            s.dv, s.dlam, dw = self._solve_kkt(W, Sigma, s.J, -(s.grad_phi + s.JTlam), -s.c, dw_last)
+        except RuntimeError:
+            return -1.0, 0.0, 0.0, 0.0, 0.0
+        finally:
+            self.kkt_seconds += time.perf_counter() - t_kkt
+        a_max, a_z = self._bound_steps(mu, tau)
+        return dw, a_max, a_z, float(s.grad_phi @ s.dv), float(self._barrier(s.v, 0.0, mu))
+
+    def _trial(self, alpha, mu):
+        """The trial point v + alpha dv: scaled f, sum |c|, mu x barrier sum there."""
+        s = self.st
+        s.vt = s.v + alpha * s.dv
+        with np.errstate(all="ignore"):
+            s.ft, s.ct = self._f(s.vt[:self.n]), self._c(s.vt)
+            return s.ft, float(np.sum(np.abs(s.ct))), float(self._barrier(s.vt, 0.0, mu))
+
+    def _soc(self, alpha, first, mu, tau):
+        """Second-order correction after ``_trial`` rejected the step of size alpha (IPOPT A-5.7 .. A-5.9): the last
+        factorisation solved again for the constraint values alpha c + c(trial) (``first``) or alpha c_soc + c(trial) of
+        the previous corrected trial.  The corrected step replaces the Newton step for ``_trial`` / ``_accept``.
+        Returns alpha_max, alpha_z and whether the solve failed."""
+        s = self.st
+        if first:
+            s.newton_step = (s.dv, s.dlam, s.dzl, s.dzu)
+        s.c_soc = alpha * (s.c if first else s.c_soc) + s.ct
+        try:
+            dv, dlam = self._resolve_kkt(-(s.grad_phi + s.JTlam), -s.c_soc, s.v, s.lam)
+        except RuntimeError:
+            return 0.0, 0.0, True
+        if not (np.all(np.isfinite(dv)) and np.all(np.isfinite(dlam))):
+            return 0.0, 0.0, True
+        s.dv, s.dlam = dv, dlam
+        return (*self._bound_steps(mu, tau), False)
+
+    def _soc_restore(self, mu, tau):
+        """The Newton step back in place of the rejected corrections."""
+        s = self.st
+        s.dv, s.dlam, s.dzl, s.dzu = s.newton_step
+
+    def _accept(self, alpha, a_z, mu):
+        """Accept the last trial point: v, lambda (+= alpha), z (+= alpha_z, kept within a factor of the primal
+        estimates); grad f and J at the new v."""
+        s = self.st
+        s.v = s.v + alpha * s.dv
+        s.lam = s.lam + alpha * s.dlam
+        zl, zu = s.zl + a_z * s.dzl, s.zu + a_z * s.dzu
+        ks = 1e10
+        dlv, duv = np.where(self.hasl, s.v - self.vl, 1.0), np.where(self.hasu, self.vu - s.v, 1.0)
+        s.zl = np.where(self.hasl, np.clip(zl, mu / (ks * dlv), ks * mu / dlv), 0.0)
+        s.zu = np.where(self.hasu, np.clip(zu, mu / (ks * duv), ks * mu / duv), 0.0)
+        s.f, s.c = s.ft, s.ct
+        s.g = np.concatenate([self._g(s.v[:self.n]), np.zeros(self.ns)])
+        s.J = self._J(s.v[:self.n])
+
+    def _start_at(self, v, zl, zu):
+        """Everything anew at v (the start, after a restoration, after a barrier restart): grad f, J, the least-squares
+        multipliers, then the state and its scaled f and sum |c|."""
+        s = self.st
+        s.g = np.concatenate([self._g(v[:self.n]), np.zeros(self.ns)])
+        s.J = self._J(v[:self.n])
+        self._set_state(v, self._ls_multipliers(s.J, s.g - zl + zu), zl, zu)
+        return self._eval_point()
+
     # ---- main loop --------------------------------------------------------------------------------
     def solve(self, x0) -> IpmResult:
         t_start = time.perf_counter()
-        n, nv, m = self.n, self.nv, self.m
+        n, m = self.n, self.m
+        self.st = SimpleNamespace()
         x0 = np.asarray(x0, float)
         # gradient-based scaling at the starting point, IPOPT's default nlp_scaling_method (the reference leaves it
         # on, pycollo/backend.py:1704-1710): objective and every constraint row are scaled down so that no
@@ -299,47 +431,40 @@ class InteriorPointSolver:
         v = np.concatenate([x0, np.zeros(self.ns)])
         if self.ns:
             v[n:] = (self.sc * np.asarray(self.p.constraints(x0), float))[self.ineq]
-        v = self._push_interior(v, 1e-3, 1e-3) if self.warm_start else self._push_interior(v)
+        v = self._push_interior(v, *push)
         v[self.fixed] = self.vl[self.fixed]
         mu = self.mu_init
-        zl = np.where(self.hasl, 1.0, 0.0)
-        zu = np.where(self.hasu, 1.0, 0.0)
-        f, g = self._f(v[:n]), np.concatenate([self._g(v[:n]), np.zeros(self.ns)])
-        c, J = self._c(v), self._J(v[:n])
-        lam = self._ls_multipliers(J, g - zl + zu)
+        f, theta0 = self._start_at(v, np.where(self.hasl, 1.0, 0.0), np.where(self.hasu, 1.0, 0.0))
         filt: list[tuple[float, float]] = []
-        theta0 = float(np.sum(np.abs(c)))
         theta_max, theta_min = 1e4 * max(1.0, theta0), 1e-4 * max(1.0, theta0)
         dw_last = 0.0
         status, hist = "max_iter", []
         k_eps, k_mu, th_mu, s_max, g_th, g_phi, eta = 10.0, 0.2, 1.5, 100.0, 1e-5, 1e-8, 1e-4
-        accept_count = 0
-        restarts = 0
-        it = 0
+        accept_count = restarts = restorations = it = 0
         last_alpha = last_amax = 0.0
         last_tag = ""
         inf_pr = inf_du = np.inf
+        nz = max(1, int(self.hasl.sum() + self.hasu.sum()))
+        any_l, any_u = bool(self.hasl.any()), bool(self.hasu.any())
 
-        def errors(mu_):
-            dL = (g + JTlam - zl + zu)[self.free]
-            nz = max(1, int(self.hasl.sum() + self.hasu.sum()))
-            sd = max(s_max, (np.sum(np.abs(lam)) + np.sum(zl) + np.sum(zu)) / (m + nz)) / s_max
-            scz = max(s_max, (np.sum(zl) + np.sum(zu)) / nz) / s_max
+        def errors(e, mu_):
+            sd = max(s_max, (e[7] + e[8] + e[9]) / (m + nz)) / s_max
+            scz = max(s_max, (e[8] + e[9]) / nz) / s_max
             comp = 0.0
-            with np.errstate(invalid="ignore"):   # (inf x 0 where there is no bound: masked out)
-                if self.hasl.any():
-                    comp = max(comp, float(np.max(np.abs(((v - self.vl) * zl - mu_)[self.hasl]))))
-                if self.hasu.any():
-                    comp = max(comp, float(np.max(np.abs(((self.vu - v) * zu - mu_)[self.hasu]))))
-            e_du = float(np.max(np.abs(dL))) if self.nf else 0.0
-            e_pr = float(np.max(np.abs(c))) if m else 0.0
+            if any_l:
+                comp = max(comp, abs(e[3] - mu_), abs(e[4] - mu_))
+            if any_u:
+                comp = max(comp, abs(e[5] - mu_), abs(e[6] - mu_))
+            e_du = float(e[0]) if self.nf else 0.0
+            e_pr = float(e[1]) if m else 0.0
             return max(e_du / sd, e_pr, comp / scz), e_pr, e_du
 
-        phase = {"setup": time.perf_counter() - t_start, "errors": 0.0, "line_search": 0.0}
+        phase = {"setup": time.perf_counter() - t_start, "errors": 0.0, "line_search": 0.0, "newton": 0.0}
         for it in range(self.max_iter + 1):
-            JTlam = self._JT(J, lam)
             t_ph = time.perf_counter()
-            e0, inf_pr, inf_du = errors(0.0)
+            e = self._errors()
+            theta = float(e[2])
+            e0, inf_pr, inf_du = errors(e, 0.0)
             phase["errors"] += time.perf_counter() - t_ph
             hist.append((it, f, inf_pr, inf_du, mu))
             if self.verbose:
@@ -354,33 +479,20 @@ class InteriorPointSolver:
                 break
             if it == self.max_iter:
                 break
-            while errors(mu)[0] <= k_eps * mu and mu > self.tol / 10:
+            while errors(e, mu)[0] <= k_eps * mu and mu > self.tol / 10:
                 mu = max(self.tol / 10, min(k_mu * mu, mu ** th_mu))
                 filt = []
             tau = max(0.99, 1.0 - mu)
-            # Newton step
-            dlv, duv = np.where(self.hasl, v - self.vl, 1.0), np.where(self.hasu, self.vu - v, 1.0)
-            Sigma = np.where(self.hasl, zl / dlv, 0.0) + np.where(self.hasu, zu / duv, 0.0)
-            W = self._W(v[:n], lam)
-            grad_phi = g - np.where(self.hasl, mu / dlv, 0.0) + np.where(self.hasu, mu / duv, 0.0)
-            t_kkt = time.perf_counter()
-            try:
-                dv, dlam, dw_last = self._solve_kkt(W, Sigma, J, -(grad_phi + JTlam), -c, dw_last)
-            except RuntimeError:
+            t_ph = time.perf_counter()
+            dw, a_max, a_z, dphi, mub = self._newton(mu, tau, dw_last)
+            phase["newton"] += time.perf_counter() - t_ph
+            if dw < 0.0:
                 status = "kkt_failure"
                 break
-            finally:
-                self.kkt_seconds += time.perf_counter() - t_kkt
-            dzl = np.where(self.hasl, mu / dlv - zl - zl / dlv * dv, 0.0)
-            dzu = np.where(self.hasu, mu / duv - zu + zu / duv * dv, 0.0)
-            a_max = self._alpha_max(v, dv, tau)
-            a_z = min(self._alpha_dual(zl[self.hasl], dzl[self.hasl], tau) if self.hasl.any() else 1.0,
-                      self._alpha_dual(zu[self.hasu], dzu[self.hasu], tau) if self.hasu.any() else 1.0)
+            dw_last = dw
+            phi = f + mub
             # filter line search
             t_ph = time.perf_counter()
-            theta = float(np.sum(np.abs(c)))
-            phi = self._barrier(v, f, mu)
-            dphi = float(grad_phi @ dv)
             alpha, accepted = a_max, False
             a_min = 1e-12
 
@@ -396,14 +508,13 @@ class InteriorPointSolver:
                 ok = th_t_ <= (1 - g_th) * theta or phi_t_ <= phi - g_phi * theta
                 return ok, ok
 
+            def trial(a):
+                ft_, th_t_, mub_t = self._trial(a, mu)
+                return ft_, th_t_, ft_ + mub_t
+
             first = True
             while alpha > a_min:
-                vt = v + alpha * dv
-                with np.errstate(all="ignore"):
-                    ft = self._f(vt[:n])
-                    ct = self._c(vt)
-                    th_t = float(np.sum(np.abs(ct)))
-                    phi_t = self._barrier(vt, ft, mu)
+                ft, th_t, phi_t = trial(alpha)
                 accepted, augment = acceptable(alpha, ft, th_t, phi_t)
                 if self.verbose >= 2 and first:
                     print(f"      first trial: alpha {alpha:.2e} theta {theta:.3e} -> {th_t:.3e}  phi {phi:.10e} -> {phi_t:.10e}  dphi {dphi:.3e} "
@@ -417,40 +528,28 @@ class InteriorPointSolver:
                     # Second-order correction (IPOPT A-5.7 .. A-5.9): the full step was rejected and did not even reduce
                     # the violation -- the linearisation of c is what fails.  Up to four corrected steps from the same
                     # factorisation, each aimed at the violation the previous trial point was left with.
-                    c_soc, th_old, a_soc = alpha * c + ct, theta, alpha
-                    for _ in range(4):
+                    th_old, a_soc = theta, alpha
+                    for p_soc in range(4):
                         self.counts["second_order_corrections"] = self.counts.get("second_order_corrections", 0) + 1
-                        try:
-                            dv_s, dlam_s = self._resolve_kkt(-(grad_phi + JTlam), -c_soc, v, lam)
-                        except RuntimeError:
+                        a_soc, a_z_s, failed = self._soc(a_soc, p_soc == 0, mu, tau)
+                        if failed:
                             break
-                        if not (np.all(np.isfinite(dv_s)) and np.all(np.isfinite(dlam_s))):
-                            break
-                        a_soc = self._alpha_max(v, dv_s, tau)
-                        vs = v + a_soc * dv_s
-                        with np.errstate(all="ignore"):
-                            fs = self._f(vs[:n])
-                            cs = self._c(vs)
-                            th_s = float(np.sum(np.abs(cs)))
-                            phi_s = self._barrier(vs, fs, mu)
+                        fs, th_s, phi_s = trial(a_soc)
                         ok_s, augment = acceptable(alpha, fs, th_s, phi_s)
                         if self.verbose >= 2:
                             print(f"      correction: alpha {a_soc:.2e} theta -> {th_s:.3e}  phi -> {phi_s:.10e}  accepted {ok_s}")
                         if ok_s:
                             if augment:
                                 filt.append(((1 - g_th) * theta, phi - g_phi * theta))
-                            accepted, dv, dlam, alpha, vt, ft, ct = True, dv_s, dlam_s, a_soc, vs, fs, cs
-                            dzl = np.where(self.hasl, mu / dlv - zl - zl / dlv * dv, 0.0)
-                            dzu = np.where(self.hasu, mu / duv - zu + zu / duv * dv, 0.0)
-                            a_z = min(self._alpha_dual(zl[self.hasl], dzl[self.hasl], tau) if self.hasl.any() else 1.0,
-                                      self._alpha_dual(zu[self.hasu], dzu[self.hasu], tau) if self.hasu.any() else 1.0)
+                            accepted, alpha, a_z, ft = True, a_soc, a_z_s, fs
                             self.counts["second_order_steps"] = self.counts.get("second_order_steps", 0) + 1
                             break
                         if not np.isfinite(th_s) or th_s > 0.99 * th_old:
                             break
-                        c_soc, th_old = a_soc * c_soc + cs, th_s
+                        th_old = th_s
                     if accepted:
                         break
+                    self._soc_restore(mu, tau)
                 first = False
                 alpha *= 0.5
             phase["line_search"] += time.perf_counter() - t_ph
@@ -462,13 +561,18 @@ class InteriorPointSolver:
                 self.counts["acceptable_after_failed_line_search"] = 1   # (surfaced by solve_ocp: not the requested tolerance)
                 break
             if not accepted:
-                # feasibility restoration, reduced to its core: Gauss-Newton steps on ||c||_1 (minimum-norm
-                # solution of the linearised constraints, fraction-to-the-boundary, backtracking) until the
-                # violation has dropped by a tenth and the point is acceptable to the filter
+                # feasibility restoration, reduced to its core, on host vectors (rare: a resident state comes to the host
+                # for it): Gauss-Newton steps on ||c||_1 (minimum-norm solution of the linearised constraints,
+                # fraction-to-the-boundary, backtracking) until the violation has dropped by a tenth and the point is
+                # acceptable to the filter
+                v, lam, zl, zu, c, _ = self._get_state()
                 filt.append(((1 - g_th) * theta, phi - g_phi * theta))
-                vr, cr_, Jr, ok_r = v.copy(), c, J, False
+                vr, cr_, ok_r = v.copy(), c, False
                 for _ in range(30):
                     th_r = float(np.sum(np.abs(cr_)))
+                    # J at the restoration point: on the device-resident paths the line search's trial points (and the
+                    # Newton step's Hessian) have left G~ of another point behind
+                    Jr = self._J(vr[:n])
                     try:
                         dr = self._gn_step(Jr, cr_)
                     except RuntimeError:
@@ -487,7 +591,6 @@ class InteriorPointSolver:
                         a *= 0.5
                     if not moved:
                         break
-                    Jr = self._J(vr[:n])
                     th_t = float(np.sum(np.abs(cr_)))
                     if th_t <= 0.9 * theta:
                         with np.errstate(all="ignore"):
@@ -496,7 +599,10 @@ class InteriorPointSolver:
                         if np.isfinite(phi_t) and not any(th_t >= th_f and phi_t >= ph_f for th_f, ph_f in filt):
                             ok_r = True
                             break
-                if not ok_r:
+                if ok_r:
+                    restorations += 1
+                    v, last_tag = vr, " R"        # (multipliers after restoration: least squares, as at the start)
+                else:
                     # The Gauss-Newton restoration could not find a point the filter accepts.  Before giving the NLP up:
                     # a barrier restart from the best restoration point -- mu back up (two decades, at most mu_init), the
                     # filter emptied, multipliers re-estimated and the bound multipliers put back on the central path
@@ -513,45 +619,29 @@ class InteriorPointSolver:
                     filt = []
                     # the fraction-to-the-boundary steps can have left components ON a bound in floating point: back
                     # inside by the distance the new central path keeps from it, then everything at that point anew
-                    v = self._push_interior(v, min(1e-2, mu), min(1e-2, mu))
-                    c, J, f = self._c(v), self._J(v[:n]), self._f(v[:n])
-                    g = np.concatenate([self._g(v[:n]), np.zeros(self.ns)])
+                    v, last_tag = self._push_interior(v, min(1e-2, mu), min(1e-2, mu)), " r"
                     dlv, duv = np.where(self.hasl, v - self.vl, 1.0), np.where(self.hasu, self.vu - v, 1.0)
                     zl = np.where(self.hasl, mu / dlv, 0.0)
                     zu = np.where(self.hasu, mu / duv, 0.0)
-                    lam = self._ls_multipliers(J, g - zl + zu)
-                    last_alpha, last_amax, last_tag = 0.0, a_max, " r"
-                    continue
-                v, c, J, f = vr, cr_, Jr, ft
-                last_alpha, last_amax, last_tag = 0.0, a_max, " R"
-                g = np.concatenate([self._g(v[:n]), np.zeros(self.ns)])
-                # multipliers after restoration: least squares, as at the start
-                lam = self._ls_multipliers(J, g - zl + zu)
+                last_alpha, last_amax = 0.0, a_max
+                f, _ = self._start_at(v, zl, zu)
                 continue
             last_alpha, last_amax, last_tag = alpha, a_max, ""
-            v = v + alpha * dv
-            lam = lam + alpha * dlam
-            zl = zl + a_z * dzl
-            zu = zu + a_z * dzu
-            # keep the duals within a factor of the primal estimates
-            ks = 1e10
-            dlv, duv = np.where(self.hasl, v - self.vl, 1.0), np.where(self.hasu, self.vu - v, 1.0)
-            zl = np.where(self.hasl, np.clip(zl, mu / (ks * dlv), ks * mu / dlv), 0.0)
-            zu = np.where(self.hasu, np.clip(zu, mu / (ks * duv), ks * mu / duv), 0.0)
-            f, c = ft, ct
-            g = np.concatenate([self._g(v[:n]), np.zeros(self.ns)])
-            J = self._J(v[:n])
+            self._accept(alpha, a_z, mu)
+            f = ft
+        v, lam, zl, zu, _, _ = self._get_state()
         ev = dict(self.counts)
         ev["barrier_restarts"] = restarts
+        ev["restorations"] = restorations                 # successful Gauss-Newton restorations
         ev["kkt_seconds"] = self.kkt_seconds
-        ev["phase_seconds"] = {k: round(v, 6) for k, v in phase.items()}   # wall time by part of the loop (with kkt_seconds)
+        ev["phase_seconds"] = {k: round(val, 6) for k, val in phase.items()}   # wall time by part of the loop (with kkt_seconds)
         return IpmResult(x=v[:n].copy(), lam=(self.sc * lam / self.sf).copy(), objective=f / self.sf, status=status, iterations=it, inf_pr=inf_pr,
                          inf_du=inf_du, mu=mu, seconds=time.perf_counter() - t_start, evaluations=ev, history=hist,
                          zl=(zl[:n] / self.sf).copy(), zu=(zu[:n] / self.sf).copy())
 
 
 class GpuInteriorPointSolver(InteriorPointSolver):
-    """The same algorithm with its linear algebra on the GPU.
+    """The same loop with its linear algebra on the GPU.
 
     G~ and H~ are evaluated into device memory (``NlpEngine.evaluate_resident``) and consumed there by the block
     L D L^T of ``pycollo_amd.kkt.GpuKkt``; what crosses the bus per iteration is a handful of vectors (x~, lambda,
@@ -665,332 +755,125 @@ class GpuInteriorPointSolver(InteriorPointSolver):
         sol = self._refined_solve(np.concatenate([np.zeros(nv), -c]), dvec, False)
         return np.where(self.fixed, 0.0, sol[:nv])
 
+    def _release(self):
+        if self.kkt is not None:
+            self.kkt.close()
+            self.kkt = None
+
     def solve(self, x0) -> IpmResult:
         self.engine.set_prefetch_jac(False)     # G~ is consumed where it is produced
         try:
             res = super().solve(x0)
         finally:
             self.engine.set_prefetch_jac(True)
+            self._release()
         res.evaluations["gpu_seconds"] = dict(self.times)
-        if self.kkt is not None:
-            self.kkt.close()
-            self.kkt = None
         return res
 
 
-class _IpmDesc(__import__("ctypes").Structure):
-    import ctypes as _C
-    _fields_ = [("n", _C.c_int64), ("m", _C.c_int64), ("ns", _C.c_int64), ("ineq_rows", _C.c_void_p),
-                ("vl", _C.c_void_p), ("vu", _C.c_void_p), ("hasl", _C.c_void_p), ("hasu", _C.c_void_p), ("fixed", _C.c_void_p),
-                ("row_scale", _C.c_void_p), ("rhs_c", _C.c_void_p), ("obj_scale", _C.c_double)]
+class _IpmDesc(C.Structure):
+    _fields_ = [("n", C.c_int64), ("m", C.c_int64), ("ns", C.c_int64), ("ineq_rows", C.c_void_p),
+                ("vl", C.c_void_p), ("vu", C.c_void_p), ("hasl", C.c_void_p), ("hasu", C.c_void_p), ("fixed", C.c_void_p),
+                ("row_scale", C.c_void_p), ("rhs_c", C.c_void_p), ("obj_scale", C.c_double)]
 
 
 class ResidentInteriorPointSolver(GpuInteriorPointSolver):
-    """The same algorithm with the ITERATION on the device as well (``csrc/pc_ipm.hpp``): v, lambda, z, the step and
-    every right-hand side stay in device memory; per iteration this loop makes four or five C calls -- error measures,
-    Newton step (Hessian, assembly, factorisation with the regularisation loop, refined solve, step limits), one call
-    per line-search trial point, acceptance -- and reads a handful of scalars.  The filter, the barrier update and the
-    termination tests are the scalar logic of :meth:`InteriorPointSolver.solve`, unchanged; the rare restoration branch
-    pulls the state to the host, runs the parent's code and pushes it back.  The reference's boundary: one call into
-    IPOPT per solve (pycollo/backend.py:1807-1827)."""
+    """The same loop with the ITERATE on the device as well (``csrc/pc_ipm.hpp``): v, lambda, z, the step and every
+    right-hand side stay in device memory, and each step of :class:`InteriorPointSolver` is the ``pc_ipm_*`` call of
+    its name -- per iteration four or five C calls (error measures; Newton step with Hessian, assembly, factorisation
+    and its regularisation loop, refined solve, step limits; one call per line-search trial point; acceptance) and a
+    handful of scalars read.  For the rare restoration branch the loop pulls the state to the host and pushes the
+    result back.  The reference's boundary: one call into IPOPT per solve (pycollo/backend.py:1807-1827)."""
+
+    _ipm = None
+
+    def _check(self, ok):
+        if not ok:
+            raise RuntimeError(self.engine._lib.pc_last_error().decode())
+
+    def _ensure_ipm(self):
+        """The device state, made once the scaling is known (at the first ``_set_state``)."""
+        if self._ipm is None:
+            lib, vp, dbl = self.engine._lib, C.c_void_p, C.c_double
+            for name, args in (("create", [vp] * 4), ("set_state", [vp] * 5), ("get_state", [vp] * 7), ("eval_point", [vp, vp]),
+                               ("errors", [vp, vp]), ("newton", [vp, dbl, dbl, dbl, vp]), ("trial", [vp, dbl, dbl, vp]),
+                               ("accept", [vp, dbl, dbl, dbl]), ("soc", [vp, dbl, C.c_int, dbl, dbl, vp]), ("soc_restore", [vp, dbl, dbl])):
+                fn = getattr(lib, "pc_ipm_" + name)
+                fn.restype, fn.argtypes = C.c_int, args
+            lib.pc_ipm_destroy.restype, lib.pc_ipm_destroy.argtypes = None, [vp]
+            kkt = self._ensure_kkt()
+            keep = [np.ascontiguousarray(self.ineq, dtype=np.int64), np.ascontiguousarray(self.vl), np.ascontiguousarray(self.vu),
+                    np.ascontiguousarray(self.hasl, dtype=np.uint8), np.ascontiguousarray(self.hasu, dtype=np.uint8),
+                    np.ascontiguousarray(self.fixed, dtype=np.uint8), np.ascontiguousarray(self.sc), np.ascontiguousarray(self.rhs_c)]
+            d = _IpmDesc(self.n, self.m, self.ns, *[a.ctypes.data for a in keep], float(self.sf))
+            handle = vp()
+            self._check(lib.pc_ipm_create(self.engine._h, kkt._h, C.byref(d), C.byref(handle)))
+            self._ipm, self._lib = handle, lib
+            self._r3, self._r8, self._r10 = np.empty(3), np.empty(8), np.empty(10)
+        return self._ipm
+
+    def _release(self):
+        if self._ipm is not None:
+            self.engine._lib.pc_ipm_destroy(self._ipm)
+            self._ipm = None
+        super()._release()
 
     def solve(self, x0) -> IpmResult:
-        import ctypes as C
-        self.engine.set_prefetch_jac(False)
-        try:
-            return self._solve_resident(x0, C)
-        finally:
-            self.engine.set_prefetch_jac(True)
-            if getattr(self, "_ipm", None):
-                self.engine._lib.pc_ipm_destroy(self._ipm)
-                self._ipm = None
-            if self.kkt is not None:
-                self.kkt.close()
-                self.kkt = None
+        res = super().solve(x0)
+        res.evaluations["resident_iteration"] = True
+        return res
 
-    def _solve_resident(self, x0, C) -> IpmResult:
-        t_start = time.perf_counter()
-        lib = self.engine._lib
-        for name in ("pc_ipm_create", "pc_ipm_set_state", "pc_ipm_get_state", "pc_ipm_eval_point", "pc_ipm_errors",
-                     "pc_ipm_newton", "pc_ipm_trial", "pc_ipm_accept", "pc_ipm_soc", "pc_ipm_soc_restore"):
-            getattr(lib, name).restype = C.c_int
-        lib.pc_ipm_destroy.restype = None
-        lib.pc_ipm_destroy.argtypes = [C.c_void_p]
-        lib.pc_ipm_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.pc_ipm_set_state.argtypes = [C.c_void_p] * 5
-        lib.pc_ipm_get_state.argtypes = [C.c_void_p] * 7
-        lib.pc_ipm_eval_point.argtypes = [C.c_void_p, C.c_void_p]
-        lib.pc_ipm_errors.argtypes = [C.c_void_p, C.c_void_p]
-        lib.pc_ipm_newton.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
-        lib.pc_ipm_trial.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p]
-        lib.pc_ipm_accept.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
-        lib.pc_ipm_soc.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p]
-        lib.pc_ipm_soc_restore.argtypes = [C.c_void_p, C.c_double, C.c_double]
+    def _set_state(self, v, lam, zl, zu):
+        h = self._ensure_ipm()
+        self._check(self._lib.pc_ipm_set_state(h, *(np.ascontiguousarray(a, dtype=np.float64).ctypes.data for a in (v, lam, zl, zu))))
 
-        def check(ok):
-            if not ok:
-                raise RuntimeError(lib.pc_last_error().decode())
+    def _get_state(self):
+        nv, m = self.nv, self.m
+        out = [np.empty(nv), np.empty(m), np.empty(nv), np.empty(nv), np.empty(m), np.empty(nv)]
+        self._check(self._lib.pc_ipm_get_state(self._ipm, *(a.ctypes.data for a in out)))
+        return out
 
-        n, nv, m = self.n, self.nv, self.m
-        x0 = np.asarray(x0, float)
-        # ---- set-up on the host, exactly as InteriorPointSolver.solve: gradient-based scaling, slacks, interior push ----
-        self.sf, self.sc = 1.0, np.ones(m)
-        push = (1e-3, 1e-3) if self.warm_start else (1e-2, 1e-2)
-        x0c = self._push_interior(np.concatenate([x0, np.zeros(self.ns)]), *push)[:n]
-        x0c[self.fixed[:n]] = self.vl[:n][self.fixed[:n]]
-        g0 = np.nan_to_num(np.asarray(self.p.gradient(x0c), float), nan=0.0, posinf=0.0, neginf=0.0)
-        gmax = float(np.max(np.abs(g0))) if n else 0.0
-        if gmax > 100.0 and self.gradient_scaling:
-            self.sf = max(100.0 / gmax, 1e-8)
-        if m and self.gradient_scaling:
-            jv = np.abs(np.nan_to_num(np.asarray(self.p.jacobian(x0c), float), nan=0.0, posinf=0.0, neginf=0.0))
-            rowmax = np.zeros(m)
-            np.maximum.at(rowmax, self.jr, jv)
-            big = rowmax > 100.0
-            self.sc[big] = np.maximum(100.0 / rowmax[big], 1e-8)
-        if self.ns:
-            self.vl[n:] = np.where(self.cl[self.ineq] > -INF, self.sc[self.ineq] * self.cl[self.ineq], self.cl[self.ineq])
-            self.vu[n:] = np.where(self.cu[self.ineq] < INF, self.sc[self.ineq] * self.cu[self.ineq], self.cu[self.ineq])
-        v = np.concatenate([x0, np.zeros(self.ns)])
-        if self.ns:
-            v[n:] = (self.sc * np.asarray(self.p.constraints(x0), float))[self.ineq]
-        v = self._push_interior(v, 1e-3, 1e-3) if self.warm_start else self._push_interior(v)
-        v[self.fixed] = self.vl[self.fixed]
-        mu = self.mu_init
-        zl = np.where(self.hasl, 1.0, 0.0)
-        zu = np.where(self.hasu, 1.0, 0.0)
-        f, g = self._f(v[:n]), np.concatenate([self._g(v[:n]), np.zeros(self.ns)])
-        c, J = self._c(v), self._J(v[:n])
-        lam = self._ls_multipliers(J, g - zl + zu)
-        # ---- the device state ----
-        kkt = self._ensure_kkt()
-        keep = [np.ascontiguousarray(self.ineq, dtype=np.int64), np.ascontiguousarray(self.vl), np.ascontiguousarray(self.vu),
-                np.ascontiguousarray(self.hasl, dtype=np.uint8), np.ascontiguousarray(self.hasu, dtype=np.uint8),
-                np.ascontiguousarray(self.fixed, dtype=np.uint8), np.ascontiguousarray(self.sc), np.ascontiguousarray(self.rhs_c)]
-        d = _IpmDesc(n, m, self.ns, *[a.ctypes.data for a in keep], float(self.sf))
-        handle = C.c_void_p()
-        check(lib.pc_ipm_create(self.engine._h, kkt._h, C.byref(d), C.byref(handle)))
-        self._ipm = handle
+    def _eval_point(self):
+        # (grad J and G~ at this point were counted when _start_at asked for them)
+        self.counts["objective"] += 1
+        self.counts["constraints"] += 1
+        self._check(self._lib.pc_ipm_eval_point(self._ipm, self._r3.ctypes.data))
+        return float(self._r3[0]), float(self._r3[1])
 
-        def push_state():
-            check(lib.pc_ipm_set_state(handle, *(np.ascontiguousarray(a, dtype=np.float64).ctypes.data for a in (v, lam, zl, zu))))
+    def _errors(self):
+        self._check(self._lib.pc_ipm_errors(self._ipm, self._r10.ctypes.data))
+        return self._r10.copy()
 
-        def pull_state():
-            out = [np.empty(nv), np.empty(m), np.empty(nv), np.empty(nv), np.empty(m), np.empty(nv)]
-            check(lib.pc_ipm_get_state(handle, *(a.ctypes.data for a in out)))
-            return out
+    def _newton(self, mu, tau, dw_last):
+        r8 = self._r8
+        t_kkt = time.perf_counter()
+        self.counts["hessian"] += 1
+        self._check(self._lib.pc_ipm_newton(self._ipm, mu, tau, dw_last, r8.ctypes.data))
+        self.kkt_seconds += time.perf_counter() - t_kkt
+        self.counts["factorisations"] += int(r8[5])
+        self.counts["kkt_solves"] = self.counts.get("kkt_solves", 0) + int(r8[6])
+        self.counts["refined_solves"] = self.counts.get("refined_solves", 0) + 1
+        return float(r8[0]), float(r8[1]), float(r8[2]), float(r8[3]), float(r8[4])
 
-        r3, r8, r10 = np.empty(3), np.empty(8), np.empty(10)
-        push_state()
-        check(lib.pc_ipm_eval_point(handle, r3.ctypes.data))
-        f, theta = float(r3[0]), float(r3[1])
-        filt: list[tuple[float, float]] = []
-        theta0 = theta
-        theta_max, theta_min = 1e4 * max(1.0, theta0), 1e-4 * max(1.0, theta0)
-        dw_last = 0.0
-        status, hist = "max_iter", []
-        k_eps, k_mu, th_mu, s_max, g_th, g_phi, eta = 10.0, 0.2, 1.5, 100.0, 1e-5, 1e-8, 1e-4
-        accept_count = restarts = it = 0
-        last_alpha = last_amax = 0.0
-        last_tag = ""
-        inf_pr = inf_du = np.inf
-        nz = max(1, int(self.hasl.sum() + self.hasu.sum()))
-        any_l, any_u = bool(self.hasl.any()), bool(self.hasu.any())
+    def _trial(self, alpha, mu):
+        self.counts["objective"] += 1
+        self.counts["constraints"] += 1
+        self._check(self._lib.pc_ipm_trial(self._ipm, alpha, mu, self._r3.ctypes.data))
+        return float(self._r3[0]), float(self._r3[1]), float(self._r3[2])
 
-        def errors(e, mu_):
-            sd = max(s_max, (e[7] + e[8] + e[9]) / (m + nz)) / s_max
-            scz = max(s_max, (e[8] + e[9]) / nz) / s_max
-            comp = 0.0
-            if any_l:
-                comp = max(comp, abs(e[3] - mu_), abs(e[4] - mu_))
-            if any_u:
-                comp = max(comp, abs(e[5] - mu_), abs(e[6] - mu_))
-            e_du = float(e[0]) if self.nf else 0.0
-            e_pr = float(e[1]) if m else 0.0
-            return max(e_du / sd, e_pr, comp / scz), e_pr, e_du
+    def _soc(self, alpha, first, mu, tau):
+        r8 = self._r8
+        self._check(self._lib.pc_ipm_soc(self._ipm, alpha, 1 if first else 0, mu, tau, r8.ctypes.data))
+        self.counts["kkt_solves"] = self.counts.get("kkt_solves", 0) + int(r8[6])
+        return float(r8[1]), float(r8[2]), r8[7] != 0.0
 
-        phase = {"setup": time.perf_counter() - t_start, "errors": 0.0, "line_search": 0.0, "newton": 0.0}
-        for it in range(self.max_iter + 1):
-            t_ph = time.perf_counter()
-            check(lib.pc_ipm_errors(handle, r10.ctypes.data))
-            e = r10.copy()
-            theta = float(e[2])
-            e0, inf_pr, inf_du = errors(e, 0.0)
-            phase["errors"] += time.perf_counter() - t_ph
-            hist.append((it, f, inf_pr, inf_du, mu))
-            if self.verbose:
-                print(f"{it:4d}  f {f: .8e}  inf_pr {inf_pr:.2e}  inf_du {inf_du:.2e}  lg(mu) {np.log10(mu):5.1f}  dw {dw_last:.1e}"
-                      f"  alpha {last_alpha:.2e} (max {last_amax:.2e}){last_tag}")
-            if e0 <= self.tol:
-                status = "optimal"
-                break
-            accept_count = accept_count + 1 if e0 <= self.acceptable_tol else 0
-            if accept_count >= 15:
-                status = "acceptable"
-                break
-            if it == self.max_iter:
-                break
-            while errors(e, mu)[0] <= k_eps * mu and mu > self.tol / 10:
-                mu = max(self.tol / 10, min(k_mu * mu, mu ** th_mu))
-                filt = []
-            tau = max(0.99, 1.0 - mu)
-            t_kkt = time.perf_counter()
-            self.counts["hessian"] += 1
-            check(lib.pc_ipm_newton(handle, mu, tau, dw_last, r8.ctypes.data))
-            dt = time.perf_counter() - t_kkt
-            self.kkt_seconds += dt
-            phase["newton"] += dt
-            self.counts["factorisations"] += int(r8[5])
-            self.counts["kkt_solves"] = self.counts.get("kkt_solves", 0) + int(r8[6])
-            self.counts["refined_solves"] = self.counts.get("refined_solves", 0) + 1
-            if r8[0] < 0.0:
-                status = "kkt_failure"
-                break
-            dw_last, a_max, a_z, dphi = float(r8[0]), float(r8[1]), float(r8[2]), float(r8[3])
-            phi = f + float(r8[4])
-            # filter line search: the scalar logic of InteriorPointSolver.solve, one device call per trial point
-            t_ph = time.perf_counter()
-            alpha, accepted = a_max, False
-            ft = th_t = phi_t = np.nan
+    def _soc_restore(self, mu, tau):
+        self._check(self._lib.pc_ipm_soc_restore(self._ipm, mu, tau))
 
-            def acceptable(alpha_, ft_, th_t_, phi_t_):
-                # (InteriorPointSolver.solve's test; the second value says the filter is to be augmented)
-                if not (np.isfinite(ft_) and np.isfinite(th_t_) and np.isfinite(phi_t_) and th_t_ <= theta_max):
-                    return False, False
-                if any(th_t_ >= th_f and phi_t_ >= ph_f for th_f, ph_f in filt):
-                    return False, False
-                if dphi < 0 and alpha_ * (-dphi) ** 2.3 > theta ** 1.1 and theta <= theta_min:
-                    return phi_t_ <= phi + eta * alpha_ * dphi, False
-                ok = th_t_ <= (1 - g_th) * theta or phi_t_ <= phi - g_phi * theta
-                return ok, ok
-
-            def trial(a):
-                self.counts["objective"] += 1
-                self.counts["constraints"] += 1
-                check(lib.pc_ipm_trial(handle, a, mu, r3.ctypes.data))
-                return float(r3[0]), float(r3[1]), float(r3[0]) + float(r3[2])
-
-            first = True
-            while alpha > 1e-12:
-                ft, th_t, phi_t = trial(alpha)
-                accepted, augment = acceptable(alpha, ft, th_t, phi_t)
-                if self.verbose >= 2 and first:
-                    print(f"      first trial: alpha {alpha:.2e} theta {theta:.3e} -> {th_t:.3e}  phi {phi:.10e} -> {phi_t:.10e}  dphi {dphi:.3e} accepted {accepted}")
-                if accepted:
-                    if augment:
-                        filt.append(((1 - g_th) * theta, phi - g_phi * theta))
-                    break
-                if first and self.second_order_correction and np.isfinite(th_t) and th_t >= theta:
-                    # second-order correction on the device (pc_ipm_soc): up to four corrected steps from the same factors
-                    th_old, a_soc, r8s = theta, alpha, np.empty(8)
-                    for p_soc in range(4):
-                        self.counts["second_order_corrections"] = self.counts.get("second_order_corrections", 0) + 1
-                        check(lib.pc_ipm_soc(handle, a_soc, 1 if p_soc == 0 else 0, mu, tau, r8s.ctypes.data))
-                        self.counts["kkt_solves"] = self.counts.get("kkt_solves", 0) + int(r8s[6])
-                        if r8s[7] != 0.0:
-                            break
-                        a_soc = float(r8s[1])
-                        fs, th_s, phi_s = trial(a_soc)
-                        ok_s, augment = acceptable(alpha, fs, th_s, phi_s)
-                        if self.verbose >= 2:
-                            print(f"      correction: alpha {a_soc:.2e} theta -> {th_s:.3e}  phi -> {phi_s:.10e}  accepted {ok_s}")
-                        if ok_s:
-                            if augment:
-                                filt.append(((1 - g_th) * theta, phi - g_phi * theta))
-                            accepted, alpha, a_z, ft, th_t, phi_t = True, a_soc, float(r8s[2]), fs, th_s, phi_s
-                            self.counts["second_order_steps"] = self.counts.get("second_order_steps", 0) + 1
-                            break
-                        if not np.isfinite(th_s) or th_s > 0.99 * th_old:
-                            break
-                        th_old = th_s
-                    if accepted:
-                        break
-                    check(lib.pc_ipm_soc_restore(handle, mu, tau))
-                first = False
-                alpha *= 0.5
-            phase["line_search"] += time.perf_counter() - t_ph
-            if not accepted and e0 <= self.acceptable_tol:
-                status = "acceptable"
-                self.counts["acceptable_after_failed_line_search"] = 1
-                break
-            if not accepted:
-                # restoration (rare): the state comes to the host, the parent's Gauss-Newton restoration / barrier restart
-                # runs on host vectors through the same GPU factorisation, the result goes back
-                v, lam, zl, zu, c, g = pull_state()
-                J = ("resident", 0)
-                filt.append(((1 - g_th) * theta, phi - g_phi * theta))
-                vr, cr_, Jr, ok_r = v.copy(), c, J, False
-                for _ in range(30):
-                    th_r = float(np.sum(np.abs(cr_)))
-                    self._J(vr[:n])              # G~ at the restoration point (the Newton step left the Hessian's launch behind it)
-                    try:
-                        dr = self._gn_step(Jr, cr_)
-                    except RuntimeError:
-                        break
-                    if not np.all(np.isfinite(dr)):
-                        break
-                    a = self._alpha_max(vr, dr, tau)
-                    moved = False
-                    while a > 1e-10:
-                        vt = vr + a * dr
-                        with np.errstate(all="ignore"):
-                            ct = self._c(vt)
-                        if np.all(np.isfinite(ct)) and float(np.sum(np.abs(ct))) < (1 - 1e-4 * a) * th_r:
-                            vr, cr_, moved = vt, ct, True
-                            break
-                        a *= 0.5
-                    if not moved:
-                        break
-                    th_t = float(np.sum(np.abs(cr_)))
-                    if th_t <= 0.9 * theta:
-                        with np.errstate(all="ignore"):
-                            ft = self._f(vr[:n])
-                            phi_t = self._barrier(vr, ft, mu)
-                        if np.isfinite(phi_t) and not any(th_t >= th_f and phi_t >= ph_f for th_f, ph_f in filt):
-                            ok_r = True
-                            break
-                if not ok_r:
-                    restarts += 1
-                    if restarts > 3:
-                        status = "restoration_failed"
-                        break
-                    if float(np.sum(np.abs(cr_))) < theta:
-                        v = vr
-                    mu = min(self.mu_init, max(100.0 * mu, 1e-6))
-                    filt = []
-                    v = self._push_interior(v, min(1e-2, mu), min(1e-2, mu))
-                    g = np.concatenate([self._g(v[:n]), np.zeros(self.ns)])
-                    self._J(v[:n])
-                    dlv, duv = np.where(self.hasl, v - self.vl, 1.0), np.where(self.hasu, self.vu - v, 1.0)
-                    zl = np.where(self.hasl, mu / dlv, 0.0)
-                    zu = np.where(self.hasu, mu / duv, 0.0)
-                    lam = self._ls_multipliers(J, g - zl + zu)
-                    last_alpha, last_amax, last_tag = 0.0, a_max, " r"
-                else:
-                    v = vr
-                    last_alpha, last_amax, last_tag = 0.0, a_max, " R"
-                    g = np.concatenate([self._g(v[:n]), np.zeros(self.ns)])
-                    self._J(v[:n])
-                    lam = self._ls_multipliers(J, g - zl + zu)
-                push_state()
-                check(lib.pc_ipm_eval_point(handle, r3.ctypes.data))
-                f = float(r3[0])
-                continue
-            last_alpha, last_amax, last_tag = alpha, a_max, ""
-            self.counts["gradient"] += 1
-            self.counts["jacobian"] += 1
-            check(lib.pc_ipm_accept(handle, alpha, a_z, mu))
-            f = ft
-        v, lam, zl, zu, c, g = pull_state()
-        ev = dict(self.counts)
-        ev["barrier_restarts"] = restarts
-        ev["kkt_seconds"] = self.kkt_seconds
-        ev["phase_seconds"] = {k: round(val, 6) for k, val in phase.items()}
-        ev["gpu_seconds"] = dict(self.times)
-        ev["resident_iteration"] = True
-        return IpmResult(x=v[:n].copy(), lam=(self.sc * lam / self.sf).copy(), objective=f / self.sf, status=status, iterations=it,
-                         inf_pr=inf_pr, inf_du=inf_du, mu=mu, seconds=time.perf_counter() - t_start, evaluations=ev, history=hist,
-                         zl=(zl[:n] / self.sf).copy(), zu=(zu[:n] / self.sf).copy())
+    def _accept(self, alpha, a_z, mu):
+        self.counts["gradient"] += 1
+        self.counts["jacobian"] += 1
+        self._check(self._lib.pc_ipm_accept(self._ipm, alpha, a_z, mu))
 
 
 def solve_nlp(problem_obj, x0, lb, ub, cl, cu, **options) -> IpmResult:

@@ -1,6 +1,7 @@
-"""An NLP solved by several ranks: the interior-point loop of ``ipm.GpuInteriorPointSolver`` over the section-sharded
-evaluation (``sharding.ShardedNlp.evaluate_local_device``) and the KKT factorisation cut across ranks
-(``kkt_sharded.ShardedKkt``).
+"""An NLP solved by several ranks: the one interior-point loop (``ipm.InteriorPointSolver.solve``) with the host-vector
+steps and GPU linear algebra of ``ipm.GpuInteriorPointSolver``, over the section-sharded evaluation
+(``sharding.ShardedNlp.evaluate_local_device``) and the KKT factorisation cut across ranks (``kkt_sharded.ShardedKkt``);
+``GpuInteriorPointSolver.solve`` closes the factorisation's handles whether the solve returns or raises.
 
 The reference solves on one process (pycollo/backend.py:1807-1827: one ``ca.nlpsol`` call; IPOPT + MUMPS).  Here every
 rank runs the same interior-point iteration on **replicated vectors** (x~, slacks, multipliers, steps: a few hundred KB)
@@ -189,6 +190,10 @@ def solve_sharded(iteration, group=None, max_iter: int = 500, tol: float = 1e-8,
     pobj = ShardedGpuProblem(sh, poison)
     solver = ShardedInteriorPointSolver(pobj, pobj.n, pobj.m, iteration.x_bnd_l, iteration.x_bnd_u, iteration.c_bnd_l,
                                         iteration.c_bnd_u, tol=tol, max_iter=max_iter, verbose=verbose, **opts)
-    res = solver.solve(iteration.guess_x_tilde)
+    try:
+        res = solver.solve(iteration.guess_x_tilde)
+    except BaseException:
+        sh.release()      # (the iteration's own engine must not stay restricted to this rank's tiles)
+        raise
     res.evaluations["sharded"] = {"world": sh.world, "rank": sh.rank, "evaluations": pobj.engine.evaluations}
     return res, sh

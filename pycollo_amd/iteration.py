@@ -149,7 +149,7 @@ class MeshIteration:
             from .ipm_sharded import solve_sharded
             res, sh = solve_sharded(self, max_iter=max_iter, tol=tol, verbose=verbose, warm_start=warm_start,
                                     second_order_correction=os.environ.get("PYCOLLO_AMD_SOC", "1") != "0")
-            sh.release()
+            sh.release()        # (solve_sharded has released it itself if the solve raised)
             self.result = res
             self.x_tilde = res.x
             self.objective = res.objective / self.w

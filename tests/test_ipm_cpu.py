@@ -171,3 +171,56 @@ def test_second_order_correction_takes_the_full_step():
     assert with_soc.counts.get("second_order_steps", 0) >= 1
     assert "second_order_steps" not in without.counts
     assert a.iterations <= b.iterations
+
+
+class WaechterBiegler:
+    """min x1  s.t.  x1^2 - x2 - 1 = 0,  x1 - x3 - 0.5 = 0,  x2, x3 >= 0 (Waechter & Biegler, Math. Program. 88, 2000):
+    from infeasible starting points the Newton steps run into the bounds, the line search fails and the solver has to
+    restore feasibility.  Optimum x = (1, 0, 0.5)."""
+    n, m = 3, 2
+
+    def objective(self, x):
+        return x[0]
+
+    def gradient(self, x):
+        return np.array([1.0, 0.0, 0.0])
+
+    def constraints(self, x):
+        return np.array([x[0]**2 - x[1] - 1.0, x[0] - x[2] - 0.5])
+
+    def jacobianstructure(self):
+        return np.array([0, 0, 1, 1]), np.array([0, 1, 0, 2])
+
+    def jacobian(self, x):
+        return np.array([2.0 * x[0], -1.0, 1.0, -1.0])
+
+    def hessianstructure(self):
+        return np.array([0]), np.array([0])
+
+    def hessian(self, x, lam, s):
+        return np.array([2.0 * lam[0]])
+
+
+def _solve_wb(x0):
+    s = InteriorPointSolver(WaechterBiegler(), 3, 2, [-2e19, 0.0, 0.0], [2e19, 2e19, 2e19], np.zeros(2), np.zeros(2))
+    return s.solve(np.array(x0, float))
+
+
+def test_failed_line_search_is_restored_by_gauss_newton_steps():
+    res = _solve_wb([0.5, 1.0, 1.0])
+    assert res.status == "optimal"
+    np.testing.assert_allclose(res.x, [1.0, 0.0, 0.5], atol=1e-6)
+    assert res.evaluations["restorations"] == 1 and res.evaluations["barrier_restarts"] == 0
+
+
+def test_failed_restoration_is_followed_by_a_barrier_restart():
+    res = _solve_wb([-4.0, 1.0, 1.0])
+    assert res.status == "optimal"
+    np.testing.assert_allclose(res.x, [1.0, 0.0, 0.5], atol=1e-6)
+    assert res.evaluations["barrier_restarts"] == 1 and res.evaluations["restorations"] == 0
+
+
+def test_restoration_failed_once_the_barrier_restarts_are_used_up():
+    res = _solve_wb([-2.0, 3.0, 1.0])
+    assert res.status == "restoration_failed" and not res.success
+    assert res.evaluations["barrier_restarts"] == 4 and res.evaluations["restorations"] == 0
