@@ -398,6 +398,10 @@ int pc_ipm_create(pc_handle* h, pc_kkt* k, const pc_ipm_desc* desc, pc_ipm** out
 void pc_ipm_destroy(pc_ipm* s);
 int pc_ipm_set_state(pc_ipm* s, const double* v, const double* lambda, const double* zl, const double* zu);
 int pc_ipm_get_state(pc_ipm* s, double* v, double* lambda, double* zl, double* zu, double* c, double* g);   /* NULL: skipped */
+/* read only (tests): the last linear solve's solution [dv ; dlambda] (n + ns + m), the bound multipliers' steps (n + ns
+ * each), the right-hand side (n + ns + m), the last trial point (n + ns) and the unshifted diagonal the solve was refined
+ * against (n + ns + m).  Waits for the stream, then copies; NULL: skipped */
+int pc_ipm_get_step(pc_ipm* s, double* sol, double* dzl, double* dzu, double* rhs, double* vt, double* dvec_true);
 /* evaluate J, grad J, g, jac_g at the current v; out3 = scaled objective, sum |c|, max |c| */
 int pc_ipm_eval_point(pc_ipm* s, double* out3);
 /* out10 = max |grad L| over free unknowns, max |c|, sum |c|, max / min of (v - vl) zl, max / min of (vu - v) zu,

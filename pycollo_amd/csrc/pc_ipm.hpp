@@ -387,6 +387,22 @@ int pc_ipm_get_state(pc_ipm* s, double* v, double* lam, double* zl, double* zu, 
   });
 }
 
+// the step and what it was solved from, read only (tests): the solution of the last linear solve [dv ; dlam], the bound
+// multipliers' steps, the right-hand side, the last trial point and the unshifted diagonal the solve was refined against
+int pc_ipm_get_step(pc_ipm* s, double* sol, double* dzl, double* dzu, double* rhs, double* vt, double* dvec_true) {
+  return guarded([&] {
+    if (!s) throw std::runtime_error("null argument");
+    require_device(s->h);
+    HIP_OK(hipStreamSynchronize(s->h->stream));
+    if (sol) HIP_OK(hipMemcpy(sol, s->sol.p, s->nu * sizeof(double), hipMemcpyDeviceToHost));
+    if (dzl) HIP_OK(hipMemcpy(dzl, s->dzl.p, s->nv * sizeof(double), hipMemcpyDeviceToHost));
+    if (dzu) HIP_OK(hipMemcpy(dzu, s->dzu.p, s->nv * sizeof(double), hipMemcpyDeviceToHost));
+    if (rhs) HIP_OK(hipMemcpy(rhs, s->rhs.p, s->nu * sizeof(double), hipMemcpyDeviceToHost));
+    if (vt) HIP_OK(hipMemcpy(vt, s->vt.p, s->nv * sizeof(double), hipMemcpyDeviceToHost));
+    if (dvec_true) HIP_OK(hipMemcpy(dvec_true, s->dvec_true.p, s->nu * sizeof(double), hipMemcpyDeviceToHost));
+  });
+}
+
 // f (scaled by obj_scale), theta = sum |c|, max |c| at the current point; J, grad J, c~ and G~ are evaluated there
 int pc_ipm_eval_point(pc_ipm* s, double* out3) {
   return guarded([&] {

@@ -81,7 +81,11 @@ class InteriorPointSolver:
         self.lb, self.ub = np.asarray(lb, float).copy(), np.asarray(ub, float).copy()
         self.cl, self.cu = np.asarray(cl, float).copy(), np.asarray(cu, float).copy()
         self.tol, self.acceptable_tol, self.max_iter, self.mu_init, self.verbose = tol, acceptable_tol, max_iter, mu_init, verbose
-        self.eq = np.isclose(self.cl, self.cu, rtol=0, atol=0) | (np.abs(self.cu - self.cl) <= 1e-14 * np.maximum(1.0, np.abs(self.cl)))
+        # (a bound that is infinite on one side only: without the finiteness test, -inf gives inf <= inf below and the row
+        #  would count as an equality, the variable as fixed; cl = cu = the same infinity still reads as an equality)
+        with np.errstate(invalid="ignore"):
+            self.eq = np.isclose(self.cl, self.cu, rtol=0, atol=0) | (np.isfinite(self.cl) & np.isfinite(self.cu) & (
+                np.abs(self.cu - self.cl) <= 1e-14 * np.maximum(1.0, np.abs(self.cl))))
         self.ineq = np.nonzero(~self.eq)[0]
         self.ns = len(self.ineq)
         self.nv = self.n + self.ns
@@ -90,7 +94,8 @@ class InteriorPointSolver:
         self.vu = np.concatenate([self.ub, self.cu[self.ineq]])
         # fixed variables (x^L = x^U: pinned initial states, fixed times) are parameters, as in IPOPT's default
         # fixed_variable_treatment = make_parameter: no barrier terms, no step components
-        self.fixed = (self.vu - self.vl) <= 1e-12 * np.maximum(1.0, np.abs(self.vl))
+        with np.errstate(invalid="ignore"):
+            self.fixed = np.isfinite(self.vl) & np.isfinite(self.vu) & ((self.vu - self.vl) <= 1e-12 * np.maximum(1.0, np.abs(self.vl)))
         self.free = np.nonzero(~self.fixed)[0]
         self.nf = len(self.free)
         self.hasl = (self.vl > -INF) & ~self.fixed
@@ -795,7 +800,7 @@ class ResidentInteriorPointSolver(GpuInteriorPointSolver):
         """The device state, made once the scaling is known (at the first ``_set_state``)."""
         if self._ipm is None:
             lib, vp, dbl = self.engine._lib, C.c_void_p, C.c_double
-            for name, args in (("create", [vp] * 4), ("set_state", [vp] * 5), ("get_state", [vp] * 7), ("eval_point", [vp, vp]),
+            for name, args in (("create", [vp] * 4), ("set_state", [vp] * 5), ("get_state", [vp] * 7), ("get_step", [vp] * 7), ("eval_point", [vp, vp]),
                                ("errors", [vp, vp]), ("newton", [vp, dbl, dbl, dbl, vp]), ("trial", [vp, dbl, dbl, vp]),
                                ("accept", [vp, dbl, dbl, dbl]), ("soc", [vp, dbl, C.c_int, dbl, dbl, vp]), ("soc_restore", [vp, dbl, dbl])):
                 fn = getattr(lib, "pc_ipm_" + name)
@@ -831,6 +836,14 @@ class ResidentInteriorPointSolver(GpuInteriorPointSolver):
         nv, m = self.nv, self.m
         out = [np.empty(nv), np.empty(m), np.empty(nv), np.empty(nv), np.empty(m), np.empty(nv)]
         self._check(self._lib.pc_ipm_get_state(self._ipm, *(a.ctypes.data for a in out)))
+        return out
+
+    def _get_step(self):
+        """Read only, for tests (the loop does not call it): the last linear solve's solution [dv ; dlam], dzl, dzu, its
+        right-hand side, the last trial point and the unshifted diagonal the solve was refined against."""
+        nv, nu = self.nv, self.nv + self.m
+        out = [np.empty(nu), np.empty(nv), np.empty(nv), np.empty(nu), np.empty(nv), np.empty(nu)]
+        self._check(self._lib.pc_ipm_get_step(self._ipm, *(a.ctypes.data for a in out)))
         return out
 
     def _eval_point(self):

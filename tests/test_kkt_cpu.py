@@ -36,6 +36,21 @@ def kkt_case(name, kw, seed=0, device=None):
     return eng, ora, x, lam, ineq, fixed, sc, dvec
 
 
+def ipm_like_case(name, kw, seed=0, lam_scale=100.0, dw=1e-4, device=None):
+    """A KKT system as an interior-point iteration produces it, unlike ``kkt_case``'s strongly positive definite one:
+    Sigma = z / (v - bound) spanning twenty decades on 60 % of the primal unknowns and zero on the rest (unbounded
+    unknowns), multipliers ``lam_scale`` times larger (an indefinite Hessian that the diagonal does not dominate), the
+    primal regularisation ``dw`` of the inertia loop and dc_eff = 1e-9 in the factors.  Returns ``kkt_case``'s tuple
+    with that diagonal, and the diagonal of the system the refined solve is held to (dc = 0)."""
+    eng, ora, x, lam, ineq, fixed, sc, _ = kkt_case(name, kw, seed, device)
+    nv, m = eng.num_x + len(ineq), eng.num_c
+    rng = np.random.default_rng(seed + 1000)
+    Sigma = np.where(rng.uniform(size=nv) < 0.6, 10.0 ** rng.uniform(-10.0, 10.0, nv), 0.0)
+    dvec = np.concatenate([Sigma + dw, np.full(m, -1e-9)])
+    dvec_true = np.concatenate([Sigma + dw, np.zeros(m)])
+    return eng, ora, x, lam_scale * lam, ineq, fixed, sc, dvec, dvec_true
+
+
 def reference_matrix(eng, G, H, ineq, fixed, sc, dvec):
     n, m, ns = eng.num_x, eng.num_c, len(ineq)
     hr, hc = eng.evaluate_H_structure()
