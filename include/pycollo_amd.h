@@ -485,6 +485,50 @@ int pc_check_derivatives_device(pc_handle* h, const double* d_x, double obj_fact
                                 const double* d_jac_override, const double* d_hess_override, const pc_deriv_opts* opts,
                                 pc_deriv_report* report, void* stream);
 
+/* ---- dense output of an NLP point -------------------------------------------------------------------------------
+ * replaces: CasadiSolution.extract_full_solution (pycollo/solution/casadi_solution.py:15-86: unscaled y, u, the state
+ * derivatives dy through backend.dy_iter_callable, time) and SolutionABC.interpolate_solution_lobatto / _radau
+ * (pycollo/solution/solution_abc.py:60-142: K (n_y + n_u) NumPy polynomial fits in a Python loop), and adds what the
+ * reference leaves to the caller: evaluating those polynomials at arbitrary times, on the device.
+ *
+ * Per section the state derivative and the controls are polynomials in the section variable c in [-1, 1], held by their
+ * Legendre coefficients; section k's n_k coefficients of a variable start at sec_s[k] + k of its row of N + K - 1.  The
+ * state is y(tau_k) + stretch * integral of the derivative's polynomial: at a node it is the integrated form and
+ * differs from the node's NLP value by that defect row's residual.  A query at an interior section boundary belongs to
+ * the section on its right; the end of the phase to the last section.
+ *
+ * tabD / tabU: for every listed order n an n x n table (row-major, concatenated in the order of `orders`) that takes the
+ * n node values of a section to the Legendre coefficients of the state derivative / of the control
+ * (pycollo_amd.solution.solution_tables).  tau: the node abscissae of every phase, concatenated.
+ * A solution keeps a copy of x and reads the handle's scaling at creation.  It launches on the handle's stream and must
+ * be destroyed before the handle.  None of these calls touches the handle's staged point, caches or outputs. */
+typedef struct pc_solution pc_solution;
+/* replaces casadi_solution.py:15-86 + solution_abc.py:60-142 (x: host, scaled) */
+int pc_solution_create(pc_handle* h, const double* x, int n_orders, const int32_t* orders, const double* tabD,
+                       const double* tabU, const double* tau, pc_solution** sol);
+/* the same from a device x (the resident solver's iterate); replaces casadi_solution.py:12-17, which copies x to the host */
+int pc_solution_create_device(pc_handle* h, const double* d_x, int n_orders, const int32_t* orders, const double* tabD,
+                              const double* tabU, const double* tau, pc_solution** sol);
+void pc_solution_destroy(pc_solution* sol);
+/* sizes of one phase's arrays (any output may be NULL) */
+int pc_solution_sizes(pc_solution* sol, int phase, int32_t* N, int32_t* K, int32_t* NC, int32_t* n_y, int32_t* n_u);
+/* replaces casadi_solution.py:43-86 (PhaseSolutionData.time [N], y [n_y][N], dy [n_y][N], u [n_u][N]); NULL: skipped */
+int pc_solution_nodes(pc_solution* sol, int phase, double* time, double* y, double* dy, double* u);
+/* replaces solution_abc.py:76-80,98-100,128-140 (the coefficients of dy_polys / u_polys, here both in the Legendre basis
+ * of the section variable): dy_coef [n_y][N + K - 1], u_coef [n_u][N + K - 1]; NULL: skipped */
+int pc_solution_coefficients(pc_solution* sol, int phase, double* dy_coef, double* u_coef);
+enum { PC_SOLUTION_TAU = 1, PC_SOLUTION_EXTRAPOLATE = 2 };
+/* replaces evaluating y_polys / dy_polys / u_polys of solution_abc.py:89,101 one polynomial object at a time.  t: n_t
+ * times (PC_SOLUTION_TAU: abscissae in [-1, 1]) in any order; outputs variable-major [var][n_t] in query order, NULL:
+ * skipped; f = the model's state equations at the interpolated (y, u), so that dy - f is the collocation residual
+ * between the nodes.  A query outside the phase gives NaN in every output unless PC_SOLUTION_EXTRAPOLATE is set (then
+ * the end section's polynomials are extended).  Host pointers; synchronises. */
+int pc_solution_sample(pc_solution* sol, int phase, const double* t, int64_t n_t, int flags, double* y, double* dy, double* u,
+                       double* f);
+/* the same with device pointers, queued on the handle's stream (pc_stream); does not synchronise */
+int pc_solution_sample_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_y, double* d_dy,
+                              double* d_u, double* d_f);
+
 /* timing of the last n pc_eval_all_device launches is measured by the caller with HIP events on the
  * stream it passed; this returns the stream the handle owns (hipStream_t) */
 void* pc_stream(pc_handle* h);

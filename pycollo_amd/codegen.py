@@ -307,6 +307,7 @@ def generate_source(model: Model, orders=None, heavy_cap: bool | None = None, mi
     heavy_any = any(is_heavy(pm) for pm in model.phases)
     parts = [f"// generated by pycollo_amd.codegen for model '{model.name}' digest {model.digest} -- do not edit",
              '#include "pc_kernels.hpp"',
+             '#include "pc_solution.hpp"',
              "",
              "template <int N> __device__ __forceinline__ double pc_powi(double x) {",
              "  double r = 1.0;",
@@ -484,6 +485,8 @@ def generate_source(model: Model, orders=None, heavy_cap: bool | None = None, mi
     for pm in model.phases:
         parts.append(f'extern "C" __global__ void __launch_bounds__(256) pc_mesh_err_p{pm.index}(PcRefineArgs a) '
                      f'{{ pc::mesh_error<gen::Phase{pm.index}>(a); }}')
+        # dense output of an NLP point: pc_sol_fit_p<i> and pc_sol_sample_p<i> (pc_solution.hpp; solution_abc.py:60-142)
+        parts.append(f'PC_SOL_ENTRY_POINTS({pm.index})')
     parts.append('extern "C" __global__ void __launch_bounds__(PC_TAIL_THREADS) pc_tail(const double* x, const double* partials0, '
                  'const double* scal0, long long x_off0, int n_tiles0, int N0, int flags, int block_threads, PcTailArgs a) {')
     parts.append('  const PcTailLead ld{x, partials0, scal0, x_off0, n_tiles0, N0, flags, block_threads};')
@@ -570,7 +573,7 @@ def _preload_count() -> int:
 
 def _kernels_stamp() -> str:
     h = hashlib.sha256()
-    for fn in ("pc_kernels.hpp", "pc_args.h"):
+    for fn in ("pc_kernels.hpp", "pc_solution.hpp", "pc_args.h"):
         with open(os.path.join(CSRC, fn), "rb") as f:
             h.update(f.read())
     with open(os.path.abspath(__file__), "rb") as f:   # the generator itself: printer rules, kernel entry points

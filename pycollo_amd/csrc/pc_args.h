@@ -288,4 +288,51 @@ struct PcRefineArgs {
   double scal[PC_MAX_SCAL];
 };
 
+// Arguments of the dense-output kernels (pc_solution.hpp; pycollo/solution/solution_abc.py:60-142,
+// casadi_solution.py:15-86).  A section's polynomials are held by their Legendre coefficients in the section variable
+// c in [-1, 1]; section k's n_k coefficients of a variable start at sec_s[k] + k of its row of NC = N + K - 1.
+struct PcSolFitArgs {
+  const double* x;          // [num_x] scaled NLP point
+  const double* tau;        // [N] node abscissae
+  const int32_t* tile_k0;   // [n_tiles+1] first section of every tile (sum of n_k lanes <= blockDim)
+  const int32_t* lane0;     // [K] first lane of every section inside its tile
+  const int32_t* sec_s;     // [K+1] first node of every section
+  const double* tabD;       // per order n: n x n, node values of f -> Legendre coefficients of the state derivative
+  const double* tabU;       // per order n: n x n, node values of u -> Legendre coefficients of the control
+  double* node_t;           // [N] time at the nodes
+  double* node_y;           // [NY][N] unscaled states
+  double* node_u;           // [NU][N] unscaled controls
+  double* node_f;           // [NY][N] state derivatives f(y, u, q, t, s)
+  double* coef_dy;          // [NY][NC]
+  double* coef_u;           // [NU][NC]
+  int64_t x_off, s_off;
+  double t_fixed[2];
+  int32_t N, K, NC, tab_total;
+  int32_t offC[PC_MAX_ORDER + 1];
+  double scal[PC_MAX_SCAL];
+};
+
+#define PC_SOL_TAU 1          // the queries are tau in [-1, 1], not times
+#define PC_SOL_EXTRAPOLATE 2  // a query outside the phase extends the end section's polynomials (else: NaN)
+#define PC_SOL_END_SLACK 1.7763568394002505e-15   // 8 eps: a time whose tau misses [-1, 1] by no more is the phase's end
+
+struct PcSolSampleArgs {
+  const double* x;          // [num_x] scaled NLP point (free times; the q / t / s arguments of f)
+  const double* t;          // [Q] queries, any order
+  const int32_t* sec_s;     // [K+1]
+  const double* sec_tau;    // [K+1] tau at the section boundaries
+  const double* node_y;     // [NY][N]
+  const double* coef_dy;    // [NY][NC]
+  const double* coef_u;     // [NU][NC]
+  double* out_y;            // [NY][Q] or null
+  double* out_dy;           // [NY][Q] or null
+  double* out_u;            // [NU][Q] or null
+  double* out_f;            // [NY][Q] or null: f at the interpolated (y, u)
+  int64_t Q;
+  int64_t x_off, s_off;
+  double t_fixed[2];
+  int32_t N, K, NC, flags;
+  double scal[PC_MAX_SCAL];
+};
+
 #endif  // PC_ARGS_H

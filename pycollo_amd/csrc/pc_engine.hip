@@ -1776,3 +1776,4 @@ int pc_read_symbol(pc_handle* h, const char* name, void* dst, size_t bytes) {
 
 #include "pc_ipm.hpp"   // the device-resident interior-point state (same translation unit: it uses launch_all)
 #include "pc_deriv_check.hpp"   // the derivative check (same translation unit: it uses launch_all)
+#include "pc_solution_host.hpp"   // dense output of an NLP point (same translation unit: it uses find_fn and DevBuf)

@@ -1,0 +1,244 @@
+// Dense output of an NLP point: the exported calls (include/pycollo_amd.h: pc_solution_*).  Included at the end of
+// pc_engine.hip (same translation unit: it uses the handle, find_fn and DevBuf).  The index arithmetic is
+// pc_solution_plan.hpp; the kernels are pc_solution.hpp, compiled into the model's code object.
+//
+// A solution owns a copy of the point it was made from and everything derived from it; it reads the handle's scaling
+// constants once, at creation, and launches on the handle's stream.  The handle's staged point, its callback caches and
+// its outputs are not touched: an evaluation after any of these calls returns what it returned before.
+#include "pc_solution_plan.hpp"
+
+struct pc_solution {
+  pc_handle* h = nullptr;
+  DevBuf<double> d_x;
+  struct Phase {
+    pcs::FitPlan plan;
+    DevBuf<int32_t> sec_s;
+    DevBuf<double> sec_tau, node_t, node_y, node_u, node_f, coef_dy, coef_u;
+    hipFunction_t fn_sample = nullptr;
+    PcSolSampleArgs args;   // everything but the queries, the outputs and the flags
+    int NY = 0, NU = 0;
+  };
+  std::vector<std::unique_ptr<Phase>> ph;
+};
+
+namespace {
+
+void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const double* tabD, const double* tabU,
+                    const double* tau) {
+  pc_handle* h = s->h;
+  auto& Q = h->Q;
+  if (!tabD || !tabU || !tau) throw std::runtime_error("solution: null table");
+  DevBuf<double> d_D, d_U;
+  int32_t offC[PC_MAX_ORDER + 1];
+  const int32_t tab_total = pcs::table_offsets(n_orders, orders, offC);
+  d_D.upload(std::vector<double>(tabD, tabD + tab_total));
+  d_U.upload(std::vector<double>(tabU, tabU + tab_total));
+  size_t tau_off = 0;
+  for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
+    auto& P = Q.ph[ip];
+    auto& D = *h->pd[ip];
+    auto S = std::make_unique<pc_solution::Phase>();
+    S->NY = P.n_y;
+    S->NU = P.n_u;
+    S->plan = pcs::build_fit_plan(P.K, P.n_k.data(), n_orders, orders, P.n_y, P.n_u, 256, h->lds_limit);
+    const pcs::FitPlan& F = S->plan;
+    if (F.N != P.N) throw std::runtime_error("solution: the plan's node count differs from the handle's");
+    if (D.scal_host.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
+    const std::vector<double> edges = pcs::section_edges(F, tau + tau_off);
+    DevBuf<int32_t> d_tile, d_lane;
+    DevBuf<double> d_tau;
+    d_tile.upload(F.tile_k0);
+    d_lane.upload(F.lane0);
+    d_tau.upload(std::vector<double>(tau + tau_off, tau + tau_off + P.N));
+    tau_off += (size_t)P.N;
+    S->sec_s.upload(F.sec_s);
+    S->sec_tau.upload(edges);
+    const size_t ny = (size_t)std::max(1, P.n_y), nu = (size_t)std::max(1, P.n_u);
+    S->node_t.alloc((size_t)F.N);
+    S->node_y.alloc(ny * F.N);
+    S->node_u.alloc(nu * F.N);
+    S->node_f.alloc(ny * F.N);
+    S->coef_dy.alloc(ny * F.NC);
+    S->coef_u.alloc(nu * F.NC);
+    hipFunction_t fn_fit = nullptr;
+    HIP_OK(find_fn(h, &fn_fit, ("pc_sol_fit_p" + std::to_string(ip)).c_str()));
+    HIP_OK(find_fn(h, &S->fn_sample, ("pc_sol_sample_p" + std::to_string(ip)).c_str()));
+    PcSolFitArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.x = s->d_x.p;
+    a.tau = d_tau.p;
+    a.tile_k0 = d_tile.p;
+    a.lane0 = d_lane.p;
+    a.sec_s = S->sec_s.p;
+    a.tabD = d_D.p;
+    a.tabU = d_U.p;
+    a.node_t = S->node_t.p;
+    a.node_y = S->node_y.p;
+    a.node_u = S->node_u.p;
+    a.node_f = S->node_f.p;
+    a.coef_dy = S->coef_dy.p;
+    a.coef_u = S->coef_u.p;
+    a.x_off = P.x_off;
+    a.s_off = Q.s_off;
+    a.t_fixed[0] = P.t_fixed[0];
+    a.t_fixed[1] = P.t_fixed[1];
+    a.N = F.N;
+    a.K = F.K;
+    a.NC = F.NC;
+    a.tab_total = F.tab_total;
+    for (int i = 0; i <= PC_MAX_ORDER; ++i) a.offC[i] = F.offC[i];
+    for (size_t i = 0; i < D.scal_host.size(); ++i) a.scal[i] = D.scal_host[i];
+    size_t sz = sizeof(a);
+    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+    HIP_OK(hipModuleLaunchKernel(fn_fit, F.n_tiles(), 1, 1, F.TB, 1, 1, (unsigned)F.lds_bytes, h->stream, nullptr, cfg));
+    HIP_OK(hipStreamSynchronize(h->stream));   // the tile tables above are released on return
+    PcSolSampleArgs& q = S->args;
+    std::memset(&q, 0, sizeof(q));
+    q.x = s->d_x.p;
+    q.sec_s = S->sec_s.p;
+    q.sec_tau = S->sec_tau.p;
+    q.node_y = S->node_y.p;
+    q.coef_dy = S->coef_dy.p;
+    q.coef_u = S->coef_u.p;
+    q.x_off = P.x_off;
+    q.s_off = Q.s_off;
+    q.t_fixed[0] = P.t_fixed[0];
+    q.t_fixed[1] = P.t_fixed[1];
+    q.N = F.N;
+    q.K = F.K;
+    q.NC = F.NC;
+    for (size_t i = 0; i < D.scal_host.size(); ++i) q.scal[i] = D.scal_host[i];
+    s->ph.push_back(std::move(S));
+  }
+}
+
+void solution_launch_sample(pc_solution* s, int phase, const double* d_t, int64_t n_t, int flags, double* d_y, double* d_dy,
+                            double* d_u, double* d_f) {
+  auto& S = *s->ph[phase];
+  if (n_t == 0) return;
+  PcSolSampleArgs a = S.args;
+  a.t = d_t;
+  a.Q = n_t;
+  a.flags = flags;
+  a.out_y = S.NY > 0 ? d_y : nullptr;
+  a.out_dy = S.NY > 0 ? d_dy : nullptr;
+  a.out_u = S.NU > 0 ? d_u : nullptr;
+  a.out_f = S.NY > 0 ? d_f : nullptr;
+  size_t sz = sizeof(a);
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  HIP_OK(hipModuleLaunchKernel(S.fn_sample, (unsigned)pcs::sample_blocks(n_t, 256), 1, 1, 256, 1, 1, 0, s->h->stream, nullptr, cfg));
+}
+
+int solution_create(pc_handle* h, const double* x, bool x_on_device, int n_orders, const int32_t* orders, const double* tabD,
+                    const double* tabU, const double* tau, pc_solution** out) {
+  return guarded([&] {
+    require_device(h);
+    if (!x || !out) throw std::runtime_error("solution: null argument");
+    *out = nullptr;
+    auto s = std::make_unique<pc_solution>();
+    s->h = h;
+    s->d_x.alloc((size_t)h->Q.num_x);
+    HIP_OK(hipMemcpyAsync(s->d_x.p, x, h->Q.num_x * sizeof(double), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                          h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    solution_build(s.get(), n_orders, orders, tabD, tabU, tau);
+    *out = s.release();
+  });
+}
+
+pc_solution::Phase& solution_phase(pc_solution* s, int phase) {
+  if (!s) throw std::runtime_error("null solution");
+  if (phase < 0 || phase >= (int)s->ph.size()) throw std::runtime_error("solution: phase out of range");
+  HIP_OK(hipSetDevice(s->h->device));
+  return *s->ph[phase];
+}
+
+void solution_down(double* dst, const DevBuf<double>& src, size_t count) {
+  if (dst && count) HIP_OK(hipMemcpy(dst, src.p, count * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+}  // namespace
+
+extern "C" {
+
+int pc_solution_create(pc_handle* h, const double* x, int n_orders, const int32_t* orders, const double* tabD,
+                       const double* tabU, const double* tau, pc_solution** sol) {
+  return solution_create(h, x, false, n_orders, orders, tabD, tabU, tau, sol);
+}
+
+int pc_solution_create_device(pc_handle* h, const double* d_x, int n_orders, const int32_t* orders, const double* tabD,
+                              const double* tabU, const double* tau, pc_solution** sol) {
+  return solution_create(h, d_x, true, n_orders, orders, tabD, tabU, tau, sol);
+}
+
+void pc_solution_destroy(pc_solution* sol) {
+  if (!sol) return;
+  (void)hipSetDevice(sol->h->device);
+  (void)hipStreamSynchronize(sol->h->stream);
+  delete sol;
+}
+
+int pc_solution_sizes(pc_solution* sol, int phase, int32_t* N, int32_t* K, int32_t* NC, int32_t* n_y, int32_t* n_u) {
+  return guarded([&] {
+    auto& S = solution_phase(sol, phase);
+    if (N) *N = S.plan.N;
+    if (K) *K = S.plan.K;
+    if (NC) *NC = S.plan.NC;
+    if (n_y) *n_y = S.NY;
+    if (n_u) *n_u = S.NU;
+  });
+}
+
+int pc_solution_nodes(pc_solution* sol, int phase, double* time, double* y, double* dy, double* u) {
+  return guarded([&] {
+    auto& S = solution_phase(sol, phase);
+    const size_t N = (size_t)S.plan.N;
+    solution_down(time, S.node_t, N);
+    solution_down(y, S.node_y, N * S.NY);
+    solution_down(dy, S.node_f, N * S.NY);
+    solution_down(u, S.node_u, N * S.NU);
+  });
+}
+
+int pc_solution_coefficients(pc_solution* sol, int phase, double* dy_coef, double* u_coef) {
+  return guarded([&] {
+    auto& S = solution_phase(sol, phase);
+    solution_down(dy_coef, S.coef_dy, (size_t)S.plan.NC * S.NY);
+    solution_down(u_coef, S.coef_u, (size_t)S.plan.NC * S.NU);
+  });
+}
+
+int pc_solution_sample(pc_solution* sol, int phase, const double* t, int64_t n_t, int flags, double* y, double* dy, double* u,
+                       double* f) {
+  return guarded([&] {
+    if (!sol) throw std::runtime_error("null solution");
+    pcs::check_sample_args((int)sol->ph.size(), phase, t, n_t, flags);
+    auto& S = solution_phase(sol, phase);
+    if (n_t == 0) return;
+    const size_t Qn = (size_t)n_t;
+    DevBuf<double> d_t, d_y, d_dy, d_u, d_f;
+    d_t.upload(std::vector<double>(t, t + Qn));
+    if (y && S.NY) d_y.alloc(Qn * S.NY);
+    if (dy && S.NY) d_dy.alloc(Qn * S.NY);
+    if (u && S.NU) d_u.alloc(Qn * S.NU);
+    if (f && S.NY) d_f.alloc(Qn * S.NY);
+    solution_launch_sample(sol, phase, d_t.p, n_t, flags, d_y.p, d_dy.p, d_u.p, d_f.p);
+    HIP_OK(hipStreamSynchronize(sol->h->stream));
+    if (d_y.p) solution_down(y, d_y, Qn * S.NY);
+    if (d_dy.p) solution_down(dy, d_dy, Qn * S.NY);
+    if (d_u.p) solution_down(u, d_u, Qn * S.NU);
+    if (d_f.p) solution_down(f, d_f, Qn * S.NY);
+  });
+}
+
+int pc_solution_sample_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_y, double* d_dy,
+                              double* d_u, double* d_f) {
+  return guarded([&] {
+    if (!sol) throw std::runtime_error("null solution");
+    pcs::check_sample_args((int)sol->ph.size(), phase, d_t, n_t, flags);
+    (void)solution_phase(sol, phase);
+    solution_launch_sample(sol, phase, d_t, n_t, flags, d_y, d_dy, d_u, d_f);
+  });
+}
+
+}  // extern "C"

@@ -220,6 +220,14 @@ class MeshIteration:
             ts.append(x[pl.t_off:pl.t_off + pl.n_t].copy())
         return taus, ys, us, qs, ts, x[self.layout.s_off:self.layout.s_off + self.layout.n_s].copy()
 
+    def dense_solution(self):
+        """The NLP point ``x_tilde`` as a :class:`pycollo_amd.solution.Solution` (the reference's ``Solution``,
+        pycollo/solution/casadi_solution.py:15-86, with dense output sampled on the device).  The node states and
+        controls are those of :meth:`solution`; they are unscaled with the scaling the NLP functions were generated
+        with (the engine's), which is this iteration's unless ``update_scaling`` averaged it afterwards."""
+        from .solution import Solution
+        return Solution(self.engine, self.x_tilde, objective=getattr(self, "objective", None))
+
     def solve_with_scipy(self, maxiter: int = 500, tol: float = 1e-9, verbose: int = 0):
         """Solve the scaled NLP with scipy's trust-region interior point method (stand-in for IPOPT)."""
         import scipy.sparse as sp

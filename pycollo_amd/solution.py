@@ -1,0 +1,345 @@
+"""The solution of one NLP as the user sees it: node values, and dense output sampled on the device.
+
+Restates ``CasadiSolution`` (pycollo/solution/casadi_solution.py:15-86) and the interpolants of ``SolutionABC``
+(pycollo/solution/solution_abc.py:60-142).  The attribute names and the per-phase tuples are the reference's
+(``objective``, ``initial_time``, ``final_time``, ``state``, ``state_derivative``, ``control``, ``integral``, ``time``,
+``parameter``); ``node_time`` is the reference's ``_time_`` and ``tau`` its ``tau``.  The reference fits
+``K (n_y + n_u)`` NumPy polynomials in a Python loop and leaves evaluating them to the caller; here one kernel per phase
+forms every section's Legendre coefficients (``pc_sol_fit_p<i>``) and a second evaluates them at any number of times in
+any order (``pc_sol_sample_p<i>``).
+
+What the interpolant is, per section k with n nodes, section variable c in [-1, 1], stretch = (tF - t0) / 2:
+
+* Lobatto: ``ydot`` is the degree n-1 interpolant of f(y, u, q, t, s) at the section's nodes; Radau
+  (solution_abc.py:104-142): degree n-2 through the first n-1 nodes.  ``u`` is the degree n-1 interpolant of the node
+  controls through all n nodes (the reference fits it in a monomial basis, solution_abc.py:98-100; here it is held in
+  the Legendre basis like ``ydot``).
+* ``y(tau) = y(tau_k) + stretch * int_{tau_k}^{tau} ydot``, with ``y(tau_k)`` the NLP's own value at the section's first
+  node.  **At a node, y is this integrated form**: it differs from the node's NLP value (``state``) by the residual
+  of that defect row, which is zero only to the NLP tolerance.
+* a query at an interior section boundary belongs to the section on its right; the end of the phase to the last one.
+
+It reports the NLP's variables: variables eliminated as constants are not re-inserted (the scope of
+``MeshIteration.solution()``).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+
+import numpy as np
+
+from .quadrature import LOBATTO, RADAU, QuadratureTables
+
+PC_SOLUTION_TAU = 1
+PC_SOLUTION_EXTRAPOLATE = 2
+_MP_DIGITS = 60
+
+
+def section_points(quad: QuadratureTables, n: int) -> np.ndarray:
+    """The n node abscissae of a section of order n on [-1, 1].  Lobatto: the rule's points.  Radau: its n-1 points
+    and the section's end, +1 (the rule's trailing placeholder, pycollo/quadrature.py:117-134, is not a node:
+    pycollo/mesh.py:255-265 drops it and the next section's first node closes the section)."""
+    x = np.array(quad.points(int(n)), dtype=np.float64)
+    if quad.method == RADAU:
+        x[-1] = 1.0
+    return x
+
+
+def _mp_legvander(points, deg):
+    """V[i][k] = P_k(x_i), k = 0 .. deg, in mpmath arithmetic (the doubles x_i are taken as exact)."""
+    import mpmath as mp
+    V = mp.matrix(len(points), deg + 1)
+    for i, xi in enumerate(points):
+        x = mp.mpf(float(xi))
+        p0, p1 = mp.mpf(1), x
+        for k in range(deg + 1):
+            V[i, k] = p0
+            p0, p1 = p1, ((2 * k + 3) * x * p1 - (k + 1) * p0) / (k + 2)
+    return V
+
+
+def exact_tables(method: str, n: int):
+    """(C_dy, C_u) as mpmath matrices, n x n: node values of a section -> Legendre coefficients of the interpolant.
+    C_u = inverse of the Legendre Vandermonde at the n nodes; C_dy the same for Lobatto, and for Radau the inverse at
+    the first n-1 nodes, bordered by a zero row and column (degree n-2, last node unused)."""
+    import mpmath as mp
+    quad = QuadratureTables(method)
+    x = section_points(quad, n)
+    with mp.workdps(_MP_DIGITS):
+        Cu = mp.inverse(_mp_legvander(x, n - 1))
+        if method == LOBATTO:
+            Cd = Cu.copy()
+        else:
+            Cd = mp.zeros(n, n)
+            inner = mp.inverse(_mp_legvander(x[:-1], n - 2))
+            for i in range(n - 1):
+                for j in range(n - 1):
+                    Cd[i, j] = inner[i, j]
+    return Cd, Cu
+
+
+@functools.lru_cache(maxsize=None)
+def solution_tables(method: str, n: int):
+    """(C_dy, C_u) of order n as float64 arrays [n][n]: the exact tables, rounded once.  (A float64
+    ``inv(legvander)`` costs up to several hundred eps sum |l_i(t)||f_i| in the sampled values at orders 8-19; the
+    rounded exact tables keep it near one.)  Cached per (method, order)."""
+    Cd, Cu = exact_tables(method, int(n))
+    to = lambda M: np.array([[float(M[i, j]) for j in range(M.cols)] for i in range(M.rows)], dtype=np.float64)   # noqa: E731
+    a, b = to(Cd), to(Cu)
+    a.setflags(write=False)
+    b.setflags(write=False)
+    return a, b
+
+
+def _is_torch(t) -> bool:
+    return hasattr(t, "data_ptr") and hasattr(t, "device")
+
+
+END_SLACK = 8 * np.finfo(float).eps     # csrc/pc_args.h PC_SOL_END_SLACK
+
+
+def check_queries(tau_min: float, tau_max: float, has_nan: bool, extrapolate: bool, slack: float = 0.0):
+    """The range check of :meth:`Solution.sample` on the queries' extremes in tau: inside [-1, 1] (by ``slack``:
+    a *time* within a few ulp of the phase's end is the end) unless ``extrapolate``."""
+    if has_nan:
+        raise ValueError("a query is NaN")
+    if extrapolate:
+        return
+    if not (tau_min >= -1.0 - slack and tau_max <= 1.0 + slack):
+        raise ValueError(f"queries reach tau = [{tau_min!r}, {tau_max!r}], outside the phase's [-1, 1]; pass "
+                         f"extrapolate=True to extend the end sections' polynomials")
+
+
+def _tau_extremes(q_min: float, q_max: float, is_tau: bool, t0: float, tF: float):
+    if is_tau:
+        return q_min, q_max, 0.0
+    stretch, shift = 0.5 * (tF - t0), 0.5 * (t0 + tF)
+    a, b = (q_min - shift) / stretch, (q_max - shift) / stretch
+    return min(a, b), max(a, b), END_SLACK
+
+
+def normalise_query(t, tau):
+    """(array, is_tau) of ``sample``'s two ways to say where: exactly one of ``t`` / ``tau``, one-dimensional."""
+    if (t is None) == (tau is None):
+        raise ValueError("give either t or tau, not both and not neither")
+    q = t if tau is None else tau
+    if not _is_torch(q):
+        q = np.asarray(q, dtype=np.float64)
+    if q.ndim != 1:
+        raise ValueError("queries must be one-dimensional")
+    return q, tau is not None
+
+
+class Solution:
+    """``Solution(engine, x_tilde, objective=None)``: the NLP point ``x_tilde`` (scaled; a NumPy array or a torch device
+    tensor, e.g. the resident solver's iterate) of ``engine`` as node values and dense output.  Holds device memory:
+    ``close()`` it (or let it go) before the engine is closed."""
+
+    def __init__(self, engine, x_tilde, objective=None):
+        self.engine = engine
+        self._lib = engine._lib
+        self._h = C.c_void_p()
+        self._declare(self._lib)
+        lay, model = engine.layout, engine.model
+        method = engine.quad.method
+        orders = sorted({int(n) for mesh in engine.meshes for n in np.unique(mesh.n)})
+        tabs = [solution_tables(method, n) for n in orders]
+        tabD = np.ascontiguousarray(np.concatenate([t[0].ravel() for t in tabs]))
+        tabU = np.ascontiguousarray(np.concatenate([t[1].ravel() for t in tabs]))
+        od = np.ascontiguousarray(orders, dtype=np.int32)
+        tau = np.ascontiguousarray(np.concatenate([np.asarray(m.tau, dtype=np.float64) for m in engine.meshes]))
+        if _is_torch(x_tilde):
+            import torch
+            if x_tilde.dtype != torch.float64 or x_tilde.numel() != engine.num_x or not x_tilde.is_contiguous():
+                raise ValueError(f"x_tilde must be a contiguous float64 tensor of {engine.num_x} entries")
+            torch.cuda.current_stream(x_tilde.device).synchronize()
+            ok = self._lib.pc_solution_create_device(engine._h, x_tilde.data_ptr(), len(od), od.ctypes.data, tabD.ctypes.data,
+                                                     tabU.ctypes.data, tau.ctypes.data, C.byref(self._h))
+            x_host = x_tilde.detach().cpu().numpy()
+        else:
+            x_host = np.ascontiguousarray(x_tilde, dtype=np.float64).reshape(-1)
+            if x_host.shape[0] != engine.num_x:
+                raise ValueError(f"x_tilde must have {engine.num_x} entries")
+            ok = self._lib.pc_solution_create(engine._h, x_host.ctypes.data, len(od), od.ctypes.data, tabD.ctypes.data,
+                                              tabU.ctypes.data, tau.ctypes.data, C.byref(self._h))
+        if not ok:
+            raise RuntimeError("pc_solution_create failed: " + self._lib.pc_last_error().decode())
+        # node values from the device; q, t, s unscaled here (a handful of numbers)
+        x = lay.expand_x(engine.V_ocp) * x_host + lay.expand_x(engine.r_ocp)
+        self.objective = None if objective is None else float(objective)
+        node_time, state, dstate, control, integral, time, t0s, tFs = [], [], [], [], [], [], [], []
+        for ip, (pm, pl, mesh) in enumerate(zip(model.phases, lay.phases, engine.meshes)):
+            N = pl.N
+            tt = np.empty(N)
+            y, dy, u = np.empty((pm.n_y, N)), np.empty((pm.n_y, N)), np.empty((pm.n_u, N))
+            self._check(self._lib.pc_solution_nodes(self._h, ip, tt.ctypes.data, y.ctypes.data if y.size else None,
+                                                    dy.ctypes.data if dy.size else None, u.ctypes.data if u.size else None))
+            node_time.append(tt)
+            # (casadi_solution.py:45-59: an empty 1-D array where a phase has no such variable)
+            state.append(y if pm.n_y else np.array([], dtype=float))
+            dstate.append(dy if pm.n_y else np.array([], dtype=float))
+            control.append(u if pm.n_u else np.array([], dtype=float))
+            integral.append(x[pl.q_off:pl.q_off + pm.n_q].copy())
+            tv = x[pl.t_off:pl.t_off + pl.n_t].copy()
+            time.append(tv)
+            j = 0
+            t0 = float(pm.t_fixed[0])
+            tF = float(pm.t_fixed[1])
+            if pm.t_free[0]:
+                t0 = float(tv[j])
+                j += 1
+            if pm.t_free[1]:
+                tF = float(tv[j])
+            t0s.append(t0)
+            tFs.append(tF)
+        self.tau = tuple(np.asarray(m.tau, dtype=float) for m in engine.meshes)
+        self.node_time = tuple(node_time)           # the reference's _time_
+        self.state = tuple(state)
+        self.state_derivative = tuple(dstate)
+        self.control = tuple(control)
+        self.integral = tuple(integral)
+        self.time = tuple(time)                     # the time *variables* of every phase (casadi_solution.py:38)
+        self.initial_time = tuple(t0s)
+        self.final_time = tuple(tFs)
+        self.parameter = x[lay.s_off:lay.s_off + lay.n_s].copy()
+
+    # ---- plumbing ----------------------------------------------------------------------------------
+    @staticmethod
+    def _declare(lib):
+        if getattr(lib, "_pc_solution_declared", False):
+            return
+        vp = C.c_void_p
+        i32p = C.POINTER(C.c_int32)
+        lib.pc_solution_create.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(vp)]
+        lib.pc_solution_create_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(vp)]
+        lib.pc_solution_destroy.argtypes = [vp]
+        lib.pc_solution_destroy.restype = None
+        lib.pc_solution_sizes.argtypes = [vp, C.c_int, i32p, i32p, i32p, i32p, i32p]
+        lib.pc_solution_nodes.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        lib.pc_solution_coefficients.argtypes = [vp, C.c_int, vp, vp]
+        lib.pc_solution_sample.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
+        lib.pc_solution_sample_device.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
+        lib._pc_solution_declared = True
+
+    def _check(self, ok):
+        if not ok:
+            raise RuntimeError(self._lib.pc_last_error().decode())
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            if getattr(self.engine, "_h", None):          # (a closed engine has released the stream and the module)
+                self._lib.pc_solution_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _phase(self, phase: int, need_handle: bool = True) -> int:
+        phase = int(phase)
+        if not 0 <= phase < len(self.state):
+            raise ValueError(f"phase {phase} out of range (the solution has {len(self.state)})")
+        if need_handle and not self._h:
+            raise ValueError("the solution is closed")
+        return phase
+
+    # ---- polynomials -------------------------------------------------------------------------------
+    def coefficients(self, phase: int):
+        """(dy_coef [n_y][N + K - 1], u_coef [n_u][N + K - 1]): section k's n_k Legendre coefficients in the section
+        variable start at column ``mesh.s[k] + k`` (``pc_solution_coefficients``)."""
+        phase = self._phase(phase)
+        pl = self.engine.layout.phases[phase]
+        NC = pl.N + pl.K - 1
+        dc, uc = np.empty((pl.n_y, NC)), np.empty((pl.n_u, NC))
+        self._check(self._lib.pc_solution_coefficients(self._h, phase, dc.ctypes.data if dc.size else None,
+                                                       uc.ctypes.data if uc.size else None))
+        return dc, uc
+
+    def polys(self, phase: int):
+        """``phase_polys[phase]`` of the reference (solution_abc.py:60-142) as ``(y, dy, u)`` object arrays
+        [var][K] of ``numpy.polynomial.Legendre`` over ``domain = [tau_k, tau_k+1]``, built from the exported
+        coefficients; ``y[var, k](tau)`` is the integrated form."""
+        from numpy.polynomial import Legendre
+        phase = self._phase(phase)
+        mesh, pl = self.engine.meshes[phase], self.engine.layout.phases[phase]
+        dc, uc = self.coefficients(phase)
+        stretch = 0.5 * (self.final_time[phase] - self.initial_time[phase])
+        y_p = np.empty((pl.n_y, pl.K), dtype=object)
+        dy_p = np.empty((pl.n_y, pl.K), dtype=object)
+        u_p = np.empty((pl.n_u, pl.K), dtype=object)
+        for k in range(pl.K):
+            s, n = int(mesh.s[k]), int(mesh.n[k])
+            dom = [float(mesh.tau[s]), float(mesh.tau[int(mesh.s[k + 1])])]
+            sl = slice(s + k, s + k + n)
+            for a in range(pl.n_y):
+                dy_p[a, k] = Legendre(dc[a, sl], domain=dom)
+                # integ() integrates in tau (it scales by the domain's half width itself); lbnd: zero at tau_k
+                y_p[a, k] = Legendre(dc[a, sl] * stretch, domain=dom).integ(lbnd=dom[0], k=[float(self.state[phase][a][s])])
+            for b in range(pl.n_u):
+                u_p[b, k] = Legendre(uc[b, sl], domain=dom)
+        return y_p, dy_p, u_p
+
+    # ---- dense output ------------------------------------------------------------------------------
+    def sample(self, phase: int, t=None, *, tau=None, residual: bool = False, extrapolate: bool = False):
+        """``(y [n_y][Q], ydot [n_y][Q], u [n_u][Q])`` at the Q times ``t`` (or abscissae ``tau`` in [-1, 1]) of one
+        phase, in the order given (any order, duplicates allowed); with ``residual=True`` a fourth array
+        ``ydot - f(y(t), u(t), q, t, s)`` [n_y][Q], the collocation residual between the nodes.  NumPy in, NumPy out;
+        torch device tensor in, torch tensors on that device out.  Queries outside the phase raise ``ValueError``
+        unless ``extrapolate=True`` (then the end sections' polynomials are extended); a time within 8 eps (in tau) of
+        the phase's end, such as ``node_time``'s own last entry, is the end."""
+        q, is_tau = normalise_query(t, tau)
+        phase = self._phase(phase, need_handle=False)
+        t0, tF = self.initial_time[phase], self.final_time[phase]
+        flags = (PC_SOLUTION_TAU if is_tau else 0) | (PC_SOLUTION_EXTRAPOLATE if extrapolate else 0)
+        Q = int(q.shape[0])
+        if _is_torch(q):
+            import torch
+            if q.dtype != torch.float64 or not q.is_cuda:
+                raise ValueError("a tensor of queries must be float64 on the GPU")
+            q = q.contiguous()
+            if Q:
+                has_nan = bool(torch.isnan(q).any())
+                lo, hi, slack = _tau_extremes(float(q.min()), float(q.max()), is_tau, t0, tF)
+                check_queries(lo, hi, has_nan, extrapolate, slack)
+            self._phase(phase)     # (the device is needed from here on)
+            pl = self.engine.layout.phases[phase]
+            new = lambda rows: torch.empty((rows, Q), dtype=torch.float64, device=q.device)   # noqa: E731
+            y, dy, u = new(pl.n_y), new(pl.n_y), new(pl.n_u)
+            f = new(pl.n_y) if residual else None
+            ptr = lambda a: a.data_ptr() if (a is not None and a.numel()) else None   # noqa: E731
+            torch.cuda.current_stream(q.device).synchronize()     # the handle's stream is not torch's
+            self._check(self._lib.pc_solution_sample_device(self._h, phase, ptr(q), Q, flags, ptr(y), ptr(dy), ptr(u), ptr(f)))
+            self._check(self._lib.pc_synchronize(self.engine._h))
+        else:
+            q = np.ascontiguousarray(q)
+            if Q:
+                has_nan = bool(np.isnan(q).any())
+                lo, hi, slack = _tau_extremes(0.0 if has_nan else float(q.min()), 0.0 if has_nan else float(q.max()), is_tau, t0, tF)
+                check_queries(lo, hi, has_nan, extrapolate, slack)
+            self._phase(phase)     # (the device is needed from here on)
+            pl = self.engine.layout.phases[phase]
+            y, dy, u = np.empty((pl.n_y, Q)), np.empty((pl.n_y, Q)), np.empty((pl.n_u, Q))
+            f = np.empty((pl.n_y, Q)) if residual else None
+            ptr = lambda a: a.ctypes.data if (a is not None and a.size) else None   # noqa: E731
+            self._check(self._lib.pc_solution_sample(self._h, phase, ptr(q), Q, flags, ptr(y), ptr(dy), ptr(u), ptr(f)))
+        if residual:
+            return y, dy, u, dy - f
+        return y, dy, u
+
+    def sample_f(self, phase: int, t=None, *, tau=None, extrapolate: bool = False):
+        """``pc_solution_sample`` as it is (NumPy queries): ``(y, ydot, u, f)`` with f(y(t), u(t), q, t, s) itself as
+        the fourth array, and no range check -- a query outside the phase gives NaN in every output unless
+        ``extrapolate=True``."""
+        q, is_tau = normalise_query(t, tau)
+        phase = self._phase(phase)
+        pl = self.engine.layout.phases[phase]
+        q = np.ascontiguousarray(np.asarray(q, dtype=np.float64))
+        Q = int(q.shape[0])
+        flags = (PC_SOLUTION_TAU if is_tau else 0) | (PC_SOLUTION_EXTRAPOLATE if extrapolate else 0)
+        y, dy, u, f = np.empty((pl.n_y, Q)), np.empty((pl.n_y, Q)), np.empty((pl.n_u, Q)), np.empty((pl.n_y, Q))
+        ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
+        self._check(self._lib.pc_solution_sample(self._h, phase, ptr(q), Q, flags, ptr(y), ptr(dy), ptr(u), ptr(f)))
+        return y, dy, u, f

@@ -29,6 +29,17 @@ class OcpResult:
     # mesh iterations whose NLP ended "acceptable" because a line search failed at a point already inside the acceptable
     # tolerances (ipm.py, IPOPT's STOP_AT_ACCEPTABLE_POINT): converged to acceptable_tol (1e-6), not to nlp_tol
     acceptable_after_failed_line_search: list = field(default_factory=list)
+    _solution: object = field(default=None, repr=False, compare=False)
+
+    @property
+    def solution(self):
+        """The final mesh iteration's :class:`pycollo_amd.solution.Solution` (node values, dense output), built on first
+        use and kept: a solve whose caller never asks for it pays nothing."""
+        if self._solution is None:
+            if self.final is None:
+                raise ValueError("the result holds no mesh iteration")
+            self._solution = self.final.dense_solution()
+        return self._solution
 
 
 def solve_ocp(problem, *, max_mesh_iterations: int = 10, mesh_tolerance: float = MESH_TOLERANCE, device: int = 0,
