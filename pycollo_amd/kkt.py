@@ -27,13 +27,22 @@ spent on the collocation structure (no fill-reducing heuristic, no pivot search)
 Every defect multiplier sits with the node its row ends on, i.e. next to the -W V entry that pairs it with that node's
 state, so no block's multiplier part rests on the -dc I regularisation alone.
 
+The table build is three stages, each a function of a record: ``classify`` (an NLP's unknowns -> ``NlpClassification``,
+whose ``system`` is a ``Classified``: class, block and ordering keys per unknown -- the form a rank's part and the reduced
+system of kkt_sharded.py have too), ``layout`` (``Classified`` -> ``Layout``: block order and value-buffer offsets, pure
+arithmetic), and the entry tables under the position rule ``dest_numpy`` / ``dest_library``: ``entries_from_list`` for any
+system with an explicit entry list, ``entries_of_nlp`` for a whole NLP in one pass of host C++.  ``make_tables`` puts a
+layout and entry tables together; ``build_tables`` is the three in a row.
+
 This module only builds index tables (NumPy); the numeric work is in ``csrc/pc_kkt.hip`` (``pc_kkt_*`` in
 include/pycollo_amd.h).  ``oracle/ref_kkt.py`` holds a NumPy execution of the same tables for the tests.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -82,16 +91,92 @@ class KktTables:
     chain_export: np.ndarray | None = None   # [n_chain] uint8: chain nodes that are not eliminated (kkt_sharded.py), or None
 
 
-def _node_maps(engine, group, cuts=None):
+# The field specification of the tables, in the order of ``pc_kkt_desc``: what ``_Desc``, the marshalling of ``GpuKkt`` and
+# the dtype normalisation of ``make_tables`` are made from.  (``chain_export`` is the one optional array: last in the
+# structure, NULL unless a node is exported.)
+SCALAR_FIELDS = ("nu", "nv", "n_leaf", "n_chain", "n_phase", "nb", "total_vals", "border_off")
+COUNT_FIELDS = (("n_dst", "dst"), ("n_src", "src_kind"), ("n_mv", "mv_col"))        # (field of the structure, array it counts)
+ARRAY_FIELDS = (("perm", np.int64), ("leaf_ptr", np.int64), ("chain_ptr", np.int64), ("chain_phase_ptr", np.int64),
+                ("leaf_left", np.int64), ("leafA_off", np.int64), ("leafS_off", np.int64), ("chainD_off", np.int64),
+                ("chainS_off", np.int64), ("dst", np.int64), ("run_ptr", np.int64), ("src_kind", np.int32),
+                ("src_idx", np.int32), ("src_coef", np.float64), ("diag_pos", np.int64), ("fixed", np.uint8),
+                ("mv_ptr", np.int64), ("mv_col", np.int32), ("mv_kind", np.int32), ("mv_idx", np.int32), ("mv_coef", np.float64))
+_CTYPE = {np.dtype(np.int8): C.c_int8, np.dtype(np.int64): C.c_int64, np.dtype(np.int32): C.c_int32,
+          np.dtype(np.float64): C.c_double, np.dtype(np.uint8): C.c_uint8}
+
+
+def _pointer(arr):
+    return arr.ctypes.data_as(C.POINTER(_CTYPE[arr.dtype]))
+
+
+class NodeMap(NamedTuple):
+    """One phase's nodes (``_node_maps``).  Chain nodes are counted from the phase's first."""
+    s: np.ndarray             # leaf boundaries: every ``group``-th section boundary, restarting at every cut
+    N: int                    # nodes of the phase
+    is_boundary: np.ndarray   # [N] the node is a leaf boundary
+    section: np.ndarray       # [N] the boundary at or before a node, i.e. the leaf of an interior node
+    is_cut: np.ndarray        # [len(s)] the boundary is a cut
+    chain_id: np.ndarray      # [len(s)] chain node of a boundary (the left copy of a cut)
+    leaf_left: np.ndarray     # [len(s) - 1] chain node on the left of a leaf
+    n_chain: int
+    seg_ptr: np.ndarray       # first chain node of every segment and one past the last
+
+
+@dataclass
+class Classified:
+    """A classified system: all the layout and entry stages need to know about a set of ``nu`` unknowns -- a whole NLP's,
+    one rank's part of it, or the reduced border system (kkt_sharded.py)."""
+    nu: int
+    nv: int                      # goes into ``pc_kkt_desc`` as it is (0 for a rank's part and for the reduced system)
+    cls: np.ndarray              # [nu] int8 LEAF / CHAIN / BORDER
+    blk: np.ndarray              # [nu] leaf or chain node of the unknown (0 in the border)
+    key_node: np.ndarray         # [nu] ordering inside a block: primal before dual, then node, kind, natural index
+    key_kind: np.ndarray
+    dual: np.ndarray             # [nu] bool
+    fixed: np.ndarray            # [nu] bool
+    n_leaf: int
+    n_chain: int
+    chain_phase_ptr: np.ndarray  # as in KktTables
+    leaf_left: np.ndarray
+    n_primal: int
+    n_dual: int
+    chain_export: np.ndarray | None = None
+
+
+def border_system(nu, n_primal, n_dual) -> Classified:
+    """``nu`` unknowns that are all border: one dense block."""
+    z = np.zeros(nu, np.int64)
+    return Classified(nu=nu, nv=0, cls=np.full(nu, BORDER, np.int8), blk=z, key_node=z, key_kind=z, dual=np.zeros(nu, bool),
+                      fixed=np.zeros(nu, bool), n_leaf=0, n_chain=0, chain_phase_ptr=np.zeros(1, np.int64),
+                      leaf_left=np.zeros(0, np.int64), n_primal=n_primal, n_dual=n_dual)
+
+
+@dataclass
+class NlpClassification:
+    """``classify``: the classified system of a whole NLP and what only a whole NLP has."""
+    system: Classified
+    n: int                       # NLP variables, constraint rows, slacks (system.nv = n + ns, system.nu = n + ns + m)
+    m: int
+    ns: int
+    ineq_rows: np.ndarray        # [ns] int64
+    hr: np.ndarray               # structure of H~ (lower triangle) and of G~
+    hc: np.ndarray
+    jr: np.ndarray
+    jc: np.ndarray
+    maps: list                   # NodeMap per phase
+    chain_base: np.ndarray       # [phases + 1] first chain node of a phase
+    leaf_phase_ptr: np.ndarray   # [phases + 1] first leaf of a phase
+    u_phase: np.ndarray          # [nu] the phase and node an unknown sits on (-1: none)
+    u_node: np.ndarray
+    group: list
+
+
+def _node_maps(engine, group, cuts=None) -> list[NodeMap]:
     """Per phase: leaf boundaries (every ``group``-th section boundary, restarting at every cut), node -> (is boundary,
     leaf index), and the chain numbering.  ``cuts[ip]``: interior section-boundary nodes at which the phase's chain is cut
     (the sharded factorisation, kkt_sharded.py): a cut node's unknowns go to the border, and the node stands in the
     chain twice with no unknowns -- as the last node of the segment on its left and the first of the one on its right --
-    so every segment is a chain of its own, exactly like a phase.
-
-    Returns per phase (s, N, is_b, sec, is_cut, chain_id, leaf_left, n_chain, seg_ptr): ``chain_id[i]`` the chain node of
-    boundary i (the left copy of a cut), ``leaf_left[j]`` the chain node on the left of leaf j, both counted from the
-    phase's first chain node; ``seg_ptr`` the first chain node of every segment and one past the last."""
+    so every segment is a chain of its own, exactly like a phase."""
     out = []
     for ip, (mesh, g) in enumerate(zip(engine.meshes, group)):
         s_all = np.asarray(mesh.s, dtype=np.int64)
@@ -113,7 +198,7 @@ def _node_maps(engine, group, cuts=None):
         leaf_left = (np.arange(len(s) - 1, dtype=np.int64) + upto[:-1]).astype(np.int64)
         n_chain = len(s) + int(is_cut.sum())
         seg_ptr = np.concatenate([[0], chain_id[is_cut] + 1, [n_chain]]).astype(np.int64)
-        out.append((s, N, is_b, sec, is_cut, chain_id, leaf_left, n_chain, seg_ptr))
+        out.append(NodeMap(s, N, is_b, sec, is_cut, chain_id, leaf_left, n_chain, seg_ptr))
     return out
 
 
@@ -135,22 +220,9 @@ def default_group(engine, ineq_rows) -> list[int]:
     return out
 
 
-class _Plan(C.Structure):
-    _fields_ = [("nu", C.c_int64), ("nb", C.c_int64), ("border_off", C.c_int64), ("cls", C.POINTER(C.c_int8)),
-                ("blk", C.POINTER(C.c_int64)), ("local", C.POINTER(C.c_int64)),
-                ("leafA_off", C.POINTER(C.c_int64)), ("m_l", C.POINTER(C.c_int64)), ("w_l", C.POINTER(C.c_int64)),
-                ("leaf_left", C.POINTER(C.c_int64)),
-                ("chainD_off", C.POINTER(C.c_int64)), ("nzb", C.POINTER(C.c_int64)), ("nzb_next", C.POINTER(C.c_int64)),
-                ("wc", C.POINTER(C.c_int64)), ("last_of_phase", C.POINTER(C.c_uint8))]
-
-
-def build_tables(engine, ineq_rows, fixed_v, row_scale, group=None, positions: str = "library", cuts=None,
-                 _parts: dict | None = None, _layout_only: bool = False) -> KktTables:
-    """``ineq_rows``: constraint rows with a slack (in order); ``fixed_v`` [n + ns]: primal unknowns held fixed;
-    ``row_scale`` [m]: the solver's constraint-row scaling (multiplies G~ row-wise); ``group``: mesh sections per leaf
-    (int or one per phase; default ``default_group``); ``cuts``: per phase the nodes at which the chain is cut
-    (``_node_maps``; ``n_phase`` of the result then counts chain segments).  ``_parts``: filled with the classification
-    and the entry list, for ``kkt_sharded``."""
+# ---- stage 1: classification of a whole NLP's unknowns ------------------------------------------------------------------
+def classify(engine, ineq_rows, fixed_v, group=None, cuts=None) -> NlpClassification:
+    """Leaf, chain node or border for every unknown of the NLP's KKT system (arguments as ``build_tables``)."""
     lay, model = engine.layout, engine.model
     if group is None:
         group = default_group(engine, ineq_rows)
@@ -163,37 +235,34 @@ def build_tables(engine, ineq_rows, fixed_v, row_scale, group=None, positions: s
     fixed = np.zeros(nu, bool)
     fixed[:nv] = np.asarray(fixed_v, bool)
     maps = _node_maps(engine, group, cuts)
-    chain_base = np.concatenate([[0], np.cumsum([mp[7] for mp in maps])]).astype(np.int64)   # first chain node of a phase
-    leaf_phase_ptr = np.concatenate([[0], np.cumsum([len(mp[0]) - 1 for mp in maps])]).astype(np.int64)
+    chain_base = np.concatenate([[0], np.cumsum([mp.n_chain for mp in maps])]).astype(np.int64)
+    leaf_phase_ptr = np.concatenate([[0], np.cumsum([len(mp.s) - 1 for mp in maps])]).astype(np.int64)
     n_chain, n_leaf = int(chain_base[-1]), int(leaf_phase_ptr[-1])
     # the chain's independent pieces: a phase, or with cuts a segment of one (what the tables call a phase of the chain)
-    chain_phase_ptr = np.concatenate([chain_base[ip] + mp[8][:-1] for ip, mp in enumerate(maps)] + [chain_base[-1:]]).astype(np.int64)
-    n_phase = len(chain_phase_ptr) - 1
+    chain_phase_ptr = np.concatenate([chain_base[ip] + mp.seg_ptr[:-1] for ip, mp in enumerate(maps)] + [chain_base[-1:]]).astype(np.int64)
 
     cls = np.full(nu, BORDER, np.int8)
     blk = np.zeros(nu, np.int64)
-    key_node = np.zeros(nu, np.int64)      # ordering inside a block: primal before dual, then node, kind, index
+    key_node = np.zeros(nu, np.int64)
     key_kind = np.zeros(nu, np.int64)
-    key_idx = np.arange(nu, dtype=np.int64)
     dual = np.zeros(nu, bool)
     dual[nv:] = True
-
-    u_phase = np.full(nu, -1, np.int64)     # the phase and node an unknown sits on (-1: none)
+    u_phase = np.full(nu, -1, np.int64)
     u_node = np.full(nu, -1, np.int64)
 
     def place_nodes(u, ip, nodes):
         u_phase[u], u_node[u] = ip, nodes
-        s, N, is_b, sec, is_cut, chain_id = maps[ip][:6]
-        b = is_b[nodes]
-        k = sec[nodes]
-        cls[u] = np.where(b, np.where(is_cut[k], BORDER, CHAIN), LEAF)
-        blk[u] = np.where(b, chain_base[ip] + chain_id[k], leaf_phase_ptr[ip] + k)
+        mp = maps[ip]
+        b = mp.is_boundary[nodes]
+        k = mp.section[nodes]
+        cls[u] = np.where(b, np.where(mp.is_cut[k], BORDER, CHAIN), LEAF)
+        blk[u] = np.where(b, chain_base[ip] + mp.chain_id[k], leaf_phase_ptr[ip] + k)
         key_node[u] = nodes
 
     row_slack = np.full(m, -1, np.int64)
     row_slack[ineq_rows] = np.arange(ns)
     for ip, (pl, pm) in enumerate(zip(lay.phases, model.phases)):
-        N = maps[ip][1]
+        N = maps[ip].N
         nz = pm.n_z
         u = pl.x_off + np.arange(nz * N, dtype=np.int64)
         place_nodes(u, ip, (u - pl.x_off) % N)
@@ -220,219 +289,186 @@ def build_tables(engine, ineq_rows, fixed_v, row_scale, group=None, positions: s
     cls[promoted] = BORDER
     blk[cls == BORDER] = 0
     key_node[cls == BORDER] = 0
-    leaf_left = np.concatenate([chain_base[ip] + mp[6] for ip, mp in enumerate(maps)]).astype(np.int64) \
+    leaf_left = np.concatenate([chain_base[ip] + mp.leaf_left for ip, mp in enumerate(maps)]).astype(np.int64) \
         if n_leaf else np.zeros(0, np.int64)
     jr, jc = (np.asarray(a, np.int64) for a in engine.evaluate_G_structure())
-    if _parts is not None:
-        _parts.update(cls=cls.copy(), blk=blk.copy(), key_node=key_node.copy(), key_kind=key_kind.copy(), dual=dual.copy(),
-                      fixed=fixed.copy(), n=n, m=m, ns=ns, nv=nv, nu=nu, n_leaf=n_leaf, n_chain=n_chain,
-                      chain_phase_ptr=chain_phase_ptr.copy(), leaf_left=leaf_left.copy(), maps=maps, chain_base=chain_base,
-                      leaf_phase_ptr=leaf_phase_ptr, hr=hr, hc=hc, jr=jr, jc=jc, group=list(group), u_phase=u_phase, u_node=u_node)
-    if _layout_only:     # (block order and value-buffer layout without the entry tables: what kkt_sharded needs of the whole plan)
-        e0 = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0))
-        return _finish("positions", n, nv, nu, ns, m, cls, blk, key_node, key_kind, key_idx, dual, fixed, n_leaf, n_chain,
-                       chain_phase_ptr, leaf_left, hr, hc, jr, jc, row_scale, ineq_rows, entries=e0)
-    return _finish(positions, n, nv, nu, ns, m, cls, blk, key_node, key_kind, key_idx, dual, fixed, n_leaf, n_chain,
-                   chain_phase_ptr, leaf_left, hr, hc, jr, jc, row_scale, ineq_rows)
+    system = Classified(nu=nu, nv=nv, cls=cls, blk=blk, key_node=key_node, key_kind=key_kind, dual=dual, fixed=fixed,
+                        n_leaf=n_leaf, n_chain=n_chain, chain_phase_ptr=chain_phase_ptr, leaf_left=leaf_left,
+                        n_primal=nv, n_dual=m)
+    return NlpClassification(system=system, n=n, m=m, ns=ns, ineq_rows=ineq_rows, hr=hr, hc=hc, jr=jr, jc=jc, maps=maps,
+                             chain_base=chain_base, leaf_phase_ptr=leaf_phase_ptr, u_phase=u_phase, u_node=u_node,
+                             group=list(group))
 
 
-def natural_entries(n, nv, hr, hc, jr, jc, row_scale, ineq_rows):
-    """Lower-triangle entries of K over natural unknowns as (row, column, source kind, source index, coefficient):
-    H~, the row-scaled G~, the -1 of every slack."""
-    ns = len(ineq_rows)
-    eu = np.concatenate([hr, nv + jr, nv + ineq_rows])
-    ev = np.concatenate([hc, jc, n + np.arange(ns, dtype=np.int64)])
-    ekind = np.concatenate([np.full(len(hr), SRC_H), np.full(len(jr), SRC_G), np.full(ns, SRC_ONE)]).astype(np.int32)
-    eidx = np.concatenate([np.arange(len(hr)), np.arange(len(jr)), np.zeros(ns, np.int64)]).astype(np.int64)
-    ecoef = np.concatenate([np.ones(len(hr)), np.asarray(row_scale, float)[jr], -np.ones(ns)])
-    return eu, ev, ekind, eidx, ecoef
+# ---- stage 2: block order and value-buffer layout (arithmetic on the classification, no library call) -------------------
+# ``layout``: block order (perm, leaf_ptr, chain_ptr, nb) and value-buffer offsets as in KktTables, and per unknown its index
+# inside its block (local); per leaf its unknowns m_l and the width w_l of its C (both chain nodes and the border); per
+# chain node its unknowns nzb, those of the next node of its phase nzb_next (0: last_of_phase), and wc = nzb_next + nb
+Layout = namedtuple("Layout", "sys perm leaf_ptr chain_ptr local m_l w_l nzb nzb_next wc last_of_phase "
+                              "leafA_off leafS_off chainD_off chainS_off nb border_off total_vals")
 
 
-def _finish(positions, n, nv, nu, ns, m, cls, blk, key_node, key_kind, key_idx, dual, fixed, n_leaf, n_chain,
-            chain_phase_ptr, leaf_left, hr, hc, jr, jc, row_scale, ineq_rows, entries=None, n_primal=None, n_dual=None,
-            chain_export=None):
-    """Block order, value-buffer layout and entry tables of a classified system.  ``entries``: the lower-triangle entries
-    (``natural_entries`` form, fixed unknowns already dropped) when the system is not a whole NLP's (a rank's part of a
-    sharded factorisation: ``positions`` must then be "positions" or "numpy")."""
-    n_phase = len(chain_phase_ptr) - 1
-    n_primal = nv if n_primal is None else n_primal
-    n_dual = m if n_dual is None else n_dual
-    # block order
-    order = np.lexsort((key_idx, key_kind, key_node, dual, blk, cls))
-    perm = order.astype(np.int64)
-    counts_leaf = np.bincount(blk[cls == LEAF], minlength=n_leaf) if n_leaf else np.zeros(0, np.int64)
-    counts_chain = np.bincount(blk[cls == CHAIN], minlength=n_chain)
+def _starts(base, sizes):
+    """``base`` + the exclusive prefix sums of ``sizes``, and ``base`` + their sum."""
+    c = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    return base + c[:-1], base + int(c[-1])
+
+
+def layout(S: Classified) -> Layout:
+    """Block order and value-buffer layout of a classified system: arithmetic on the classification alone."""
+    cls, blk, n_leaf = S.cls, S.blk, S.n_leaf
+    perm = np.lexsort((S.key_kind, S.key_node, S.dual, blk, cls)).astype(np.int64)    # (stable: then by natural index)
+    is_leaf, is_chain, is_border = cls == LEAF, cls == CHAIN, cls == BORDER
+    counts_leaf = np.bincount(blk[is_leaf], minlength=n_leaf) if n_leaf else np.zeros(0, np.int64)
+    counts_chain = np.bincount(blk[is_chain], minlength=S.n_chain)
     leaf_ptr = np.concatenate([[0], np.cumsum(counts_leaf)]).astype(np.int64)
     chain_ptr = np.concatenate([[0], np.cumsum(counts_chain)]).astype(np.int64)
-    nb = int(np.sum(cls == BORDER))
-    local = np.empty(nu, np.int64)          # index inside its block
-    pos = np.empty(nu, np.int64)
-    pos[perm] = np.arange(nu)
-    base_leaf, base_chain = 0, int(leaf_ptr[-1])
+    nb = int(np.sum(is_border))
+    local = np.empty(S.nu, np.int64)
+    pos = np.empty(S.nu, np.int64)
+    pos[perm] = np.arange(S.nu)
+    base_chain = int(leaf_ptr[-1])
     base_border = base_chain + int(chain_ptr[-1])
-    is_leaf, is_chain, is_border = cls == LEAF, cls == CHAIN, cls == BORDER
-    local[is_leaf] = pos[is_leaf] - base_leaf - leaf_ptr[blk[is_leaf]]
+    local[is_leaf] = pos[is_leaf] - leaf_ptr[blk[is_leaf]]
     local[is_chain] = pos[is_chain] - base_chain - chain_ptr[blk[is_chain]]
     local[is_border] = pos[is_border] - base_border
 
     nzb = counts_chain.astype(np.int64)
-    last_of_phase = np.zeros(n_chain, bool)
-    last_of_phase[chain_phase_ptr[1:] - 1] = True
+    last_of_phase = np.zeros(S.n_chain, bool)
+    last_of_phase[S.chain_phase_ptr[1:] - 1] = True
     nzb_next = np.where(last_of_phase, 0, np.concatenate([nzb[1:], [0]]))
     m_l = counts_leaf.astype(np.int64)
-    w_l = (nzb[leaf_left] + nzb[leaf_left + 1] + nb) if n_leaf else np.zeros(0, np.int64)
-    # value buffer layout
-    sizeA = m_l * (m_l + w_l)
-    sizeS = w_l * w_l
-    leafA_off = np.concatenate([[0], np.cumsum(sizeA)])[:-1] if n_leaf else np.zeros(0, np.int64)
-    o = int(np.sum(sizeA))
-    leafS_off = o + (np.concatenate([[0], np.cumsum(sizeS)])[:-1] if n_leaf else np.zeros(0, np.int64))
-    o += int(np.sum(sizeS))
+    w_l = (nzb[S.leaf_left] + nzb[S.leaf_left + 1] + nb) if n_leaf else np.zeros(0, np.int64)
     wc = nzb_next + nb
-    sizeD = nzb * (nzb + wc)
-    chainD_off = o + np.concatenate([[0], np.cumsum(sizeD)])[:-1]
-    o += int(np.sum(sizeD))
-    chainS_off = o + np.concatenate([[0], np.cumsum(wc * wc)])[:-1]
-    o += int(np.sum(wc * wc))
-    border_off = o
-    total = o + nb * nb
+    # value buffer: A | C of every leaf, their Schur blocks, D | E | F of every chain node, their Schur blocks, the border
+    leafA_off, o = _starts(0, m_l * (m_l + w_l))
+    leafS_off, o = _starts(o, w_l * w_l)
+    chainD_off, o = _starts(o, nzb * (nzb + wc))
+    chainS_off, o = _starts(o, wc * wc)
+    return Layout(sys=S, perm=perm, leaf_ptr=leaf_ptr, chain_ptr=chain_ptr, local=local, m_l=m_l, w_l=w_l, nzb=nzb,
+                  nzb_next=nzb_next, wc=wc, last_of_phase=last_of_phase, leafA_off=leafA_off, leafS_off=leafS_off,
+                  chainD_off=chainD_off, chainS_off=chainS_off, nb=nb, border_off=o, total_vals=o + nb * nb)
 
-    # ---- matrix entries (natural unknown pairs), lower triangle of K ------------------------------------------
-    def make_plan():
-        """The elimination plan as the C structure ``pc_kkt_plan`` (the arrays are kept alive by the caller)."""
-        from .engine import load_library
-        lib = load_library()
-        lib.pc_kkt_plan_positions.argtypes = [C.POINTER(_Plan), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.pc_kkt_plan_entries.argtypes = [C.POINTER(_Plan), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_void_p] * 11
-        lib.pc_kkt_last_error.restype = C.c_char_p
-        keep = [np.ascontiguousarray(a, dtype=t) for a, t in (
-            (cls, np.int8), (blk, np.int64), (local, np.int64), (leafA_off, np.int64), (m_l, np.int64), (w_l, np.int64),
-            (leaf_left, np.int64), (chainD_off, np.int64), (nzb, np.int64), (nzb_next, np.int64), (wc, np.int64),
-            (last_of_phase, np.uint8))]
-        keep = [a if a.size else np.zeros(1, a.dtype) for a in keep]
-        P = _Plan()
-        P.nu, P.nb, P.border_off = int(nu), int(nb), int(border_off)
-        for name, a in zip(("cls", "blk", "local", "leafA_off", "m_l", "w_l", "leaf_left", "chainD_off", "nzb", "nzb_next",
-                            "wc", "last_of_phase"), keep):
-            ctype = {np.dtype(np.int8): C.c_int8, np.dtype(np.int64): C.c_int64, np.dtype(np.uint8): C.c_uint8}[a.dtype]
-            setattr(P, name, a.ctypes.data_as(C.POINTER(ctype)))
-        return lib, P, keep
 
-    if positions == "library":
-        if entries is not None:
-            raise ValueError("explicit entries need positions='positions' or 'numpy'")
-        # the entry tables in one pass of host C++ (pc_kkt_plan_entries): the NumPy statement below builds them from a
-        # dozen entry-sized temporaries, sorts twice and gathers nine times -- 150 ms for 15 k nodes, and several times
-        # that whenever the allocator has to fault the temporaries in afresh, which inside a solve is every time
-        lib, P, _keepalive = make_plan()
-        hr_c, hc_c, jr_c, jc_c = (np.ascontiguousarray(a, dtype=np.int64) for a in (hr, hc, jr, jc))
-        rs_c = np.ascontiguousarray(row_scale, dtype=np.float64)
-        iq_c = np.ascontiguousarray(ineq_rows, dtype=np.int64)
-        fx_c = np.ascontiguousarray(fixed, dtype=np.uint8)
-        counts = np.zeros(3, np.int64)
+# ---- the position rule: where K[u, v] (u, v natural) lies in the value buffer ---------------------------------------------
+def dest_numpy(L: Layout, u, v):
+    """Position in the value buffer of K[u, v], vectorised; -1 where the pair has no place.  (The statement of the rule;
+    ``positions="numpy"`` selects it, the CPU tests hold the library against it.)"""
+    cls, blk, local, leaf_left = L.sys.cls, L.sys.blk, L.local, L.sys.leaf_left
+    leafA_off, m_l, w_l, chainD_off, nzb, nzb_next, wc = L.leafA_off, L.m_l, L.w_l, L.chainD_off, L.nzb, L.nzb_next, L.wc
+    cu, cv = cls[u], cls[v]
+    # order the pair so that `a` is the one eliminated first: leaf < chain < border; inside a class lower block first
+    swap = (cu > cv) | ((cu == cv) & (blk[u] > blk[v])) | ((cu == cv) & (blk[u] == blk[v]) & (local[u] < local[v]))
+    a, b = np.where(swap, v, u), np.where(swap, u, v)
+    ca, cb, ba, bb, la, lb = cls[a], cls[b], blk[a], blk[b], local[a], local[b]
+    out = np.full(len(u), -1, np.int64)
+    # leaf x leaf (same leaf): lower triangle of A (a has the larger local index after the swap rule above)
+    k = (ca == LEAF) & (cb == LEAF) & (ba == bb)
+    out[k] = leafA_off[ba[k]] + la[k] * (m_l[ba[k]] + w_l[ba[k]]) + lb[k]
+    # leaf x chain
+    k = (ca == LEAF) & (cb == CHAIN)
+    left = leaf_left[ba[k]]
+    col = np.where(bb[k] == left, lb[k], np.where(bb[k] == left + 1, nzb[left] + lb[k], -1))
+    ok = col >= 0
+    tmp = np.full(int(k.sum()), -1, np.int64)
+    tmp[ok] = leafA_off[ba[k]][ok] + la[k][ok] * (m_l[ba[k]] + w_l[ba[k]])[ok] + m_l[ba[k]][ok] + col[ok]
+    out[k] = tmp
+    # leaf x border
+    k = (ca == LEAF) & (cb == BORDER)
+    left = leaf_left[ba[k]]
+    out[k] = leafA_off[ba[k]] + la[k] * (m_l[ba[k]] + w_l[ba[k]]) + m_l[ba[k]] + nzb[left] + nzb[left + 1] + lb[k]
+    # chain x chain
+    k = (ca == CHAIN) & (cb == CHAIN) & (ba == bb)
+    out[k] = chainD_off[ba[k]] + la[k] * (nzb[ba[k]] + wc[ba[k]]) + lb[k]
+    k = (ca == CHAIN) & (cb == CHAIN) & (bb == ba + 1) & ~L.last_of_phase[ba]
+    out[k] = chainD_off[ba[k]] + la[k] * (nzb[ba[k]] + wc[ba[k]]) + nzb[ba[k]] + lb[k]
+    # chain x border
+    k = (ca == CHAIN) & (cb == BORDER)
+    out[k] = chainD_off[ba[k]] + la[k] * (nzb[ba[k]] + wc[ba[k]]) + nzb[ba[k]] + nzb_next[ba[k]] + lb[k]
+    # border x border, lower
+    k = (ca == BORDER) & (cb == BORDER)
+    out[k] = L.border_off + la[k] * L.nb + lb[k]
+    return out
 
-        def call(*outs):
-            ok = lib.pc_kkt_plan_entries(C.byref(P), int(n), int(nv), len(hr_c), hr_c.ctypes.data, hc_c.ctypes.data, len(jr_c),
-                                         jr_c.ctypes.data, jc_c.ctypes.data, rs_c.ctypes.data, int(ns), iq_c.ctypes.data,
-                                         fx_c.ctypes.data, counts.ctypes.data, *[o.ctypes.data if o is not None else None for o in outs])
-            if not ok:
-                raise RuntimeError(lib.pc_kkt_last_error().decode())
-        # one call with outputs sized for the most there can be (np.empty touches no page), trimmed afterwards
-        cap = len(hr_c) + len(jr_c) + int(ns)
-        dst, run_ptr = np.empty(cap, np.int64), np.empty(cap + 1, np.int64)
-        src_kind, src_idx, src_coef = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.float64)
-        mv_ptr, mv_col = np.empty(nu + 1, np.int64), np.empty(2 * cap, np.int32)
-        mv_kind, mv_idx, mv_coef = np.empty(2 * cap, np.int32), np.empty(2 * cap, np.int32), np.empty(2 * cap, np.float64)
-        call(dst, run_ptr, src_kind, src_idx, src_coef, mv_ptr, mv_col, mv_kind, mv_idx, mv_coef)
-        n_src, n_dst, n_mv = (int(c) for c in counts)
-        dst, run_ptr = dst[:n_dst], run_ptr[:n_dst + 1]
-        src_kind, src_idx, src_coef = src_kind[:n_src], src_idx[:n_src], src_coef[:n_src]
-        mv_col, mv_kind, mv_idx, mv_coef = mv_col[:n_mv], mv_kind[:n_mv], mv_idx[:n_mv], mv_coef[:n_mv]
-        ar = np.arange(nu, dtype=np.int64)
-        diag_pos = np.empty(nu, np.int64)
-        if not lib.pc_kkt_plan_positions(C.byref(P), nu, ar.ctypes.data, ar.ctypes.data, diag_pos.ctypes.data):
-            raise RuntimeError(lib.pc_kkt_last_error().decode())
-        return KktTables(
-            nu=nu, nv=nv, n_leaf=n_leaf, n_chain=n_chain, n_phase=n_phase, nb=nb, n_primal=n_primal, n_dual=n_dual,
-            perm=perm, leaf_ptr=leaf_ptr, chain_ptr=chain_ptr, chain_phase_ptr=chain_phase_ptr, leaf_left=leaf_left,
-            leafA_off=np.asarray(leafA_off, np.int64), leafS_off=np.asarray(leafS_off, np.int64),
-            chainD_off=np.asarray(chainD_off, np.int64), chainS_off=np.asarray(chainS_off, np.int64),
-            border_off=int(border_off), total_vals=int(total),
-            dst=dst, run_ptr=run_ptr, src_kind=src_kind, src_idx=src_idx, src_coef=src_coef, diag_pos=diag_pos,
-            fixed=fixed.astype(np.uint8), mv_ptr=mv_ptr, mv_col=mv_col, mv_kind=mv_kind, mv_idx=mv_idx, mv_coef=mv_coef, chain_export=chain_export)
 
-    # ---- the same in NumPy: the statement of the rule (positions = "numpy" / "positions"; the CPU tests hold the library
-    #      against it).  "positions" takes only the position rule from the library, as round 3's first version did.
-    if entries is None:
-        eu, ev, ekind, eidx, ecoef = natural_entries(n, nv, hr, hc, jr, jc, row_scale, ineq_rows)
-        keep = ~(fixed[eu] | fixed[ev])
-        eu, ev, ekind, eidx, ecoef = eu[keep], ev[keep], ekind[keep], eidx[keep], ecoef[keep]
-    else:
-        eu, ev, ekind, eidx, ecoef = entries
+PLAN_FIELDS = (("cls", np.int8), ("blk", np.int64), ("local", np.int64), ("leafA_off", np.int64), ("m_l", np.int64),
+               ("w_l", np.int64), ("leaf_left", np.int64), ("chainD_off", np.int64), ("nzb", np.int64), ("nzb_next", np.int64),
+               ("wc", np.int64), ("last_of_phase", np.uint8))      # the arrays of ``pc_kkt_plan``, in its order
 
-    def dest_library(u, v):
-        """The same rule as ``dest_numpy`` below in one pass of host C++ (``pc_kkt_plan_positions``): the vectorised form
-        allocates ~100 temporaries of the entry count each, and their first-touch page faults were most of a table
-        build inside a solve (95 of 110 ms at config 2)."""
-        lib, P, _keepalive = make_plan()
-        u = np.ascontiguousarray(u, dtype=np.int64)
-        v = np.ascontiguousarray(v, dtype=np.int64)
-        out = np.empty(len(u), np.int64)
-        if not lib.pc_kkt_plan_positions(C.byref(P), len(u), u.ctypes.data, v.ctypes.data, out.ctypes.data):
-            raise RuntimeError(lib.pc_kkt_last_error().decode())
-        return out
 
-    def dest_numpy(u, v):
-        """Position in the value buffer of K[u, v] (u, v natural), vectorised; -1 where the pair has no place.  (The
-        statement of the rule; ``positions="numpy"`` selects it, the CPU tests hold the library against it.)"""
-        cu, cv = cls[u], cls[v]
-        # order the pair so that `a` is the one eliminated first: leaf < chain < border; inside a class lower block first
-        swap = (cu > cv) | ((cu == cv) & (blk[u] > blk[v])) | ((cu == cv) & (blk[u] == blk[v]) & (local[u] < local[v]))
-        a, b = np.where(swap, v, u), np.where(swap, u, v)
-        ca, cb, ba, bb, la, lb = cls[a], cls[b], blk[a], blk[b], local[a], local[b]
-        out = np.full(len(u), -1, np.int64)
-        # leaf x leaf (same leaf): lower triangle of A (a has the larger local index after the swap rule above)
-        k = (ca == LEAF) & (cb == LEAF) & (ba == bb)
-        out[k] = leafA_off[ba[k]] + la[k] * (m_l[ba[k]] + w_l[ba[k]]) + lb[k]
-        # leaf x chain
-        k = (ca == LEAF) & (cb == CHAIN)
-        left = leaf_left[ba[k]]
-        col = np.where(bb[k] == left, lb[k], np.where(bb[k] == left + 1, nzb[left] + lb[k], -1))
-        ok = col >= 0
-        tmp = np.full(int(k.sum()), -1, np.int64)
-        tmp[ok] = leafA_off[ba[k]][ok] + la[k][ok] * (m_l[ba[k]] + w_l[ba[k]])[ok] + m_l[ba[k]][ok] + col[ok]
-        out[k] = tmp
-        # leaf x border
-        k = (ca == LEAF) & (cb == BORDER)
-        left = leaf_left[ba[k]]
-        out[k] = leafA_off[ba[k]] + la[k] * (m_l[ba[k]] + w_l[ba[k]]) + m_l[ba[k]] + nzb[left] + nzb[left + 1] + lb[k]
-        # chain x chain
-        k = (ca == CHAIN) & (cb == CHAIN) & (ba == bb)
-        out[k] = chainD_off[ba[k]] + la[k] * (nzb[ba[k]] + wc[ba[k]]) + lb[k]
-        k = (ca == CHAIN) & (cb == CHAIN) & (bb == ba + 1) & ~last_of_phase[ba]
-        out[k] = chainD_off[ba[k]] + la[k] * (nzb[ba[k]] + wc[ba[k]]) + nzb[ba[k]] + lb[k]
-        # chain x border
-        k = (ca == CHAIN) & (cb == BORDER)
-        out[k] = chainD_off[ba[k]] + la[k] * (nzb[ba[k]] + wc[ba[k]]) + nzb[ba[k]] + nzb_next[ba[k]] + lb[k]
-        # border x border, lower
-        k = (ca == BORDER) & (cb == BORDER)
-        out[k] = border_off + la[k] * nb + lb[k]
-        return out
+class _Plan(C.Structure):
+    _fields_ = ([(k, C.c_int64) for k in ("nu", "nb", "border_off")]
+                + [(k, C.POINTER(_CTYPE[np.dtype(t)])) for k, t in PLAN_FIELDS])
 
+
+def _library_plan(L: Layout):
+    """The layout as the C structure ``pc_kkt_plan``: (library, structure, the arrays it points into)."""
+    from .engine import load_library
+    lib = load_library()
+    lib.pc_kkt_plan_positions.argtypes = [C.POINTER(_Plan), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pc_kkt_plan_entries.argtypes = [C.POINTER(_Plan), C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_void_p] * 11
+    lib.pc_kkt_last_error.restype = C.c_char_p
+    P = _Plan()
+    P.nu, P.nb, P.border_off = int(L.sys.nu), int(L.nb), int(L.border_off)
+    keep = []
+    for name, typ in PLAN_FIELDS:
+        a = np.ascontiguousarray(getattr(L.sys if name in ("cls", "blk", "leaf_left") else L, name), dtype=typ)
+        keep.append(a if a.size else np.zeros(1, typ))
+        setattr(P, name, _pointer(keep[-1]))
+    return lib, P, keep
+
+
+def dest_library(L: Layout, u, v, plan=None):
+    """The same rule as ``dest_numpy`` in one pass of host C++ (``pc_kkt_plan_positions``): the vectorised form
+    allocates ~100 temporaries of the entry count each, and their first-touch page faults were most of a table
+    build inside a solve (95 of 110 ms at config 2).  ``plan``: a ``_library_plan(L)`` the caller already has."""
+    lib, P, _keepalive = plan or _library_plan(L)
+    u = np.ascontiguousarray(u, dtype=np.int64)
+    v = np.ascontiguousarray(v, dtype=np.int64)
+    out = np.empty(len(u), np.int64)
+    if not lib.pc_kkt_plan_positions(C.byref(P), len(u), u.ctypes.data, v.ctypes.data, out.ctypes.data):
+        raise RuntimeError(lib.pc_kkt_last_error().decode())
+    return out
+
+
+# ---- stage 3: the entry tables ----------------------------------------------------------------------------------------
+# the scatter recipe, the diagonal's positions and the symmetric CSR matrix: the fields of KktTables of these names
+EntryTables = namedtuple("EntryTables", "dst run_ptr src_kind src_idx src_coef diag_pos mv_ptr mv_col mv_kind mv_idx mv_coef")
+NO_ENTRIES = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0))
+
+
+def natural_entries(nlp: NlpClassification, row_scale):
+    """Lower-triangle entries of K over natural unknowns as (row, column, source kind, source index, coefficient):
+    H~, the row-scaled G~, the -1 of every slack -- without those of a fixed unknown."""
+    nv, ns, hr, jr, fixed = nlp.system.nv, nlp.ns, nlp.hr, nlp.jr, nlp.system.fixed
+    eu = np.concatenate([hr, nv + jr, nv + nlp.ineq_rows])
+    ev = np.concatenate([nlp.hc, nlp.jc, nlp.n + np.arange(ns, dtype=np.int64)])
+    ekind = np.concatenate([np.full(len(hr), SRC_H), np.full(len(jr), SRC_G), np.full(ns, SRC_ONE)]).astype(np.int32)
+    eidx = np.concatenate([np.arange(len(hr)), np.arange(len(jr)), np.zeros(ns, np.int64)]).astype(np.int64)
+    ecoef = np.concatenate([np.ones(len(hr)), np.asarray(row_scale, float)[jr], -np.ones(ns)])
+    keep = ~(fixed[eu] | fixed[ev])
+    return eu[keep], ev[keep], ekind[keep], eidx[keep], ecoef[keep]
+
+
+def entries_from_list(L: Layout, entries, positions: str) -> EntryTables:
+    """The entry tables of any classified system from its lower-triangle entries (``natural_entries`` form), in NumPy:
+    the statement of the rule.  ``positions``: "numpy", or "positions" to take the position rule alone from the library."""
+    if positions not in ("positions", "numpy"):
+        raise ValueError("explicit entries need positions='positions' or 'numpy'")
     dest = {"positions": dest_library, "numpy": dest_numpy}[positions]
-    d = dest(eu, ev)
+    nu = L.sys.nu
+    eu, ev, ekind, eidx, ecoef = entries
+    d = dest(L, eu, ev)
     if np.any(d < 0):
         bad = np.nonzero(d < 0)[0][0]
         raise RuntimeError(f"KKT entry ({eu[bad]}, {ev[bad]}) couples two blocks the elimination order keeps apart")
     so = np.argsort(d, kind="stable")
     d_sorted = d[so]
     first = np.concatenate([[True], d_sorted[1:] != d_sorted[:-1]]) if len(d) else np.zeros(0, bool)
-    dst = d_sorted[first]
     run_ptr = np.concatenate([np.nonzero(first)[0], [len(d_sorted)]]).astype(np.int64)
-    diag_pos = dest(np.arange(nu, dtype=np.int64), np.arange(nu, dtype=np.int64))
-
-    # ---- full symmetric CSR over natural unknowns (products) ----------------------------------------------------
+    diag_pos = dest(L, np.arange(nu, dtype=np.int64), np.arange(nu, dtype=np.int64))
+    # full symmetric CSR over natural unknowns (products)
     off = eu != ev
     ru = np.concatenate([eu, ev[off]])
     rv = np.concatenate([ev, eu[off]])
@@ -448,17 +484,63 @@ def _finish(positions, n, nv, nu, ns, m, cls, blk, key_node, key_kind, key_idx, 
     if len(ks) > 1 and np.any(ks[1:] == ks[:-1]):
         raise RuntimeError("a KKT entry occurs twice in the symmetric expansion")
     mv_ptr = np.concatenate([[0], np.cumsum(np.bincount(ru, minlength=nu))]).astype(np.int64)
+    return EntryTables(d_sorted[first], run_ptr, ekind[so], eidx[so], ecoef[so], diag_pos, mv_ptr, rv[o2], rk[o2], ri[o2], rc[o2])
 
-    return KktTables(
-        nu=nu, nv=nv, n_leaf=n_leaf, n_chain=n_chain, n_phase=n_phase, nb=nb, n_primal=n_primal, n_dual=n_dual,
-        perm=perm, leaf_ptr=leaf_ptr, chain_ptr=chain_ptr, chain_phase_ptr=chain_phase_ptr, leaf_left=leaf_left,
-        leafA_off=np.asarray(leafA_off, np.int64), leafS_off=np.asarray(leafS_off, np.int64),
-        chainD_off=np.asarray(chainD_off, np.int64), chainS_off=np.asarray(chainS_off, np.int64),
-        border_off=int(border_off), total_vals=int(total),
-        dst=dst.astype(np.int64), run_ptr=run_ptr, src_kind=ekind[so].astype(np.int32), src_idx=eidx[so].astype(np.int32),
-        src_coef=ecoef[so].astype(np.float64), diag_pos=diag_pos.astype(np.int64), fixed=fixed.astype(np.uint8),
-        mv_ptr=mv_ptr, mv_col=rv[o2].astype(np.int32), mv_kind=rk[o2].astype(np.int32), mv_idx=ri[o2].astype(np.int32),
-        mv_coef=rc[o2].astype(np.float64), chain_export=chain_export)
+
+def entries_of_nlp(L: Layout, nlp: NlpClassification, row_scale) -> EntryTables:
+    """The entry tables of a whole NLP in one pass of host C++ (``pc_kkt_plan_entries``): ``entries_from_list`` builds them
+    from a dozen entry-sized temporaries, sorts twice and gathers nine times -- 150 ms for 15 k nodes, and several times
+    that whenever the allocator has to fault the temporaries in afresh, which inside a solve is every time."""
+    lib, P, _keepalive = plan = _library_plan(L)
+    nu = L.sys.nu
+    hr, hc, jr, jc, iq = (np.ascontiguousarray(a, dtype=np.int64) for a in (nlp.hr, nlp.hc, nlp.jr, nlp.jc, nlp.ineq_rows))
+    rs = np.ascontiguousarray(row_scale, dtype=np.float64)
+    fx = np.ascontiguousarray(L.sys.fixed, dtype=np.uint8)
+    counts = np.zeros(3, np.int64)
+    # one call with outputs sized for the most there can be (np.empty touches no page), trimmed afterwards
+    cap = len(hr) + len(jr) + nlp.ns
+    dst, run_ptr = np.empty(cap, np.int64), np.empty(cap + 1, np.int64)
+    src_kind, src_idx, src_coef = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.float64)
+    mv_ptr, mv_col = np.empty(nu + 1, np.int64), np.empty(2 * cap, np.int32)
+    mv_kind, mv_idx, mv_coef = np.empty(2 * cap, np.int32), np.empty(2 * cap, np.int32), np.empty(2 * cap, np.float64)
+    outs = (dst, run_ptr, src_kind, src_idx, src_coef, mv_ptr, mv_col, mv_kind, mv_idx, mv_coef)
+    if not lib.pc_kkt_plan_entries(C.byref(P), int(nlp.n), int(L.sys.nv), len(hr), hr.ctypes.data, hc.ctypes.data, len(jr), jr.ctypes.data,
+                                   jc.ctypes.data, rs.ctypes.data, int(nlp.ns), iq.ctypes.data, fx.ctypes.data, counts.ctypes.data,
+                                   *[o.ctypes.data for o in outs]):
+        raise RuntimeError(lib.pc_kkt_last_error().decode())
+    n_src, n_dst, n_mv = (int(c) for c in counts)
+    ar = np.arange(nu, dtype=np.int64)
+    return EntryTables(dst[:n_dst], run_ptr[:n_dst + 1], src_kind[:n_src], src_idx[:n_src], src_coef[:n_src],
+                       dest_library(L, ar, ar, plan), mv_ptr, mv_col[:n_mv], mv_kind[:n_mv], mv_idx[:n_mv], mv_coef[:n_mv])
+
+
+# ---- the tables ---------------------------------------------------------------------------------------------------------
+def make_tables(L: Layout, E: EntryTables) -> KktTables:
+    """The one place a ``KktTables`` is made: every array in the type ``ARRAY_FIELDS`` states."""
+    S = L.sys
+    src = {**vars(S), **L._asdict(), **E._asdict()}
+    return KktTables(nu=S.nu, nv=S.nv, n_leaf=S.n_leaf, n_chain=S.n_chain, n_phase=len(S.chain_phase_ptr) - 1, nb=L.nb,
+                     n_primal=S.n_primal, n_dual=S.n_dual, border_off=int(L.border_off), total_vals=int(L.total_vals),
+                     chain_export=S.chain_export, **{k: np.asarray(src[k], dtype=t) for k, t in ARRAY_FIELDS})
+
+
+def system_tables(S: Classified, entries, positions: str) -> KktTables:
+    """Layout and entry tables of a classified system with an explicit entry list (``entries_from_list``)."""
+    L = layout(S)
+    return make_tables(L, entries_from_list(L, entries, positions))
+
+
+def build_tables(engine, ineq_rows, fixed_v, row_scale, group=None, positions: str = "library", cuts=None) -> KktTables:
+    """``ineq_rows``: constraint rows with a slack (in order); ``fixed_v`` [n + ns]: primal unknowns held fixed;
+    ``row_scale`` [m]: the solver's constraint-row scaling (multiplies G~ row-wise); ``group``: mesh sections per leaf
+    (int or one per phase; default ``default_group``); ``cuts``: per phase the nodes at which the chain is cut
+    (``_node_maps``; ``n_phase`` of the result then counts chain segments).  ``positions``: "library" (the entry tables
+    in one pass of host C++), or "positions" / "numpy" (``entries_from_list``)."""
+    nlp = classify(engine, ineq_rows, fixed_v, group, cuts)
+    if positions != "library":
+        return system_tables(nlp.system, natural_entries(nlp, row_scale), positions)
+    L = layout(nlp.system)
+    return make_tables(L, entries_of_nlp(L, nlp, row_scale))
 
 
 def export_shapes(T: KktTables):
@@ -477,15 +559,8 @@ def export_shapes(T: KktTables):
 
 
 class _Desc(C.Structure):
-    _i64p, _i32p, _f64p, _u8p = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8)
-    _fields_ = ([(k, C.c_int64) for k in ("nu", "nv", "n_leaf", "n_chain", "n_phase", "nb", "total_vals", "border_off",
-                                          "n_dst", "n_src", "n_mv")]
-                + [(k, C.POINTER(C.c_int64)) for k in ("perm", "leaf_ptr", "chain_ptr", "chain_phase_ptr", "leaf_left",
-                                                       "leafA_off", "leafS_off", "chainD_off", "chainS_off", "dst", "run_ptr")]
-                + [("src_kind", C.POINTER(C.c_int32)), ("src_idx", C.POINTER(C.c_int32)), ("src_coef", C.POINTER(C.c_double)),
-                   ("diag_pos", C.POINTER(C.c_int64)), ("fixed", C.POINTER(C.c_uint8)), ("mv_ptr", C.POINTER(C.c_int64)),
-                   ("mv_col", C.POINTER(C.c_int32)), ("mv_kind", C.POINTER(C.c_int32)), ("mv_idx", C.POINTER(C.c_int32)),
-                   ("mv_coef", C.POINTER(C.c_double)), ("chain_export", C.POINTER(C.c_uint8))])
+    _fields_ = ([(k, C.c_int64) for k in SCALAR_FIELDS + tuple(k for k, _ in COUNT_FIELDS)]
+                + [(k, C.POINTER(_CTYPE[np.dtype(t)])) for k, t in ARRAY_FIELDS] + [("chain_export", C.POINTER(C.c_uint8))])
 
 
 class GpuKkt:
@@ -522,25 +597,17 @@ class GpuKkt:
         lib.pc_kkt_import_solution.argtypes = [vp, vp]
         d = _Desc()
         self._keep = []
-        for k in ("nu", "nv", "n_leaf", "n_chain", "n_phase", "nb", "total_vals", "border_off"):
+        for k in SCALAR_FIELDS:
             setattr(d, k, int(getattr(T, k)))
-        d.n_dst, d.n_src, d.n_mv = len(T.dst), len(T.src_kind), len(T.mv_col)
-        for k, typ in (("perm", np.int64), ("leaf_ptr", np.int64), ("chain_ptr", np.int64), ("chain_phase_ptr", np.int64),
-                       ("leaf_left", np.int64), ("leafA_off", np.int64), ("leafS_off", np.int64), ("chainD_off", np.int64),
-                       ("chainS_off", np.int64), ("dst", np.int64), ("run_ptr", np.int64), ("src_kind", np.int32),
-                       ("src_idx", np.int32), ("src_coef", np.float64), ("diag_pos", np.int64), ("fixed", np.uint8),
-                       ("mv_ptr", np.int64), ("mv_col", np.int32), ("mv_kind", np.int32), ("mv_idx", np.int32),
-                       ("mv_coef", np.float64)):
+        for k, counted in COUNT_FIELDS:
+            setattr(d, k, len(getattr(T, counted)))
+        for k, typ in ARRAY_FIELDS:
             arr = np.ascontiguousarray(getattr(T, k), dtype=typ)
-            if arr.size == 0:
-                arr = np.zeros(1, dtype=typ)
-            self._keep.append(arr)
-            ctype = {np.int64: C.c_int64, np.int32: C.c_int32, np.float64: C.c_double, np.uint8: C.c_uint8}[typ]
-            setattr(d, k, arr.ctypes.data_as(C.POINTER(ctype)))
+            self._keep.append(arr if arr.size else np.zeros(1, dtype=typ))
+            setattr(d, k, _pointer(self._keep[-1]))
         if T.chain_export is not None and np.any(T.chain_export):
-            ce = np.ascontiguousarray(T.chain_export, dtype=np.uint8)
-            self._keep.append(ce)
-            d.chain_export = ce.ctypes.data_as(C.POINTER(C.c_uint8))
+            self._keep.append(np.ascontiguousarray(T.chain_export, dtype=np.uint8))
+            d.chain_export = _pointer(self._keep[-1])
         self._export_shapes = export_shapes(T)
         dg, dj, dh = vp(), vp(), vp()
         if not lib.pc_device_results(engine._h, C.byref(dg), C.byref(dj), C.byref(dh)):

@@ -25,13 +25,16 @@ doubles), the reduced solve, local back-substitution.  The pivot signs of all lo
 to the inertia (Sylvester), so the interior-point method's regularisation loop is unchanged.  The reference has no
 counterpart: IPOPT hands the whole matrix to MUMPS on one process (pycollo/backend.py:1703-1711).
 
-``ShardedKktPlan`` is pure NumPy (tested on CPU against a general sparse solver through ``oracle/ref_kkt.py``);
+``ShardedKktPlan`` classifies the whole NLP once (``kkt.classify`` with the cuts), derives from it a ``kkt.Classified`` per rank
+and the all-border one of the reduced system, and runs each through the stages of kkt.py (``layout``, ``entries_from_list``).  It is
+pure NumPy (tested on CPU against a general sparse solver through ``oracle/ref_kkt.py``);
 ``ShardedKkt`` runs one rank on its GPU (``pc_kkt_factor_partial`` / ``_forward_partial`` / ``_backward_partial`` /
 ``pc_kkt_border_load_factor``) and moves the two small reductions with ``torch.distributed``.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -47,6 +50,16 @@ class RankTables:
     border_red: np.ndarray   # [nb_local] position in the reduced system of every local border unknown (block order)
     export_red: list = None         # per exported chain node (ascending): reduced positions of its unknowns (block order)
     export_anchor_red: list = None  # ... and of the exported last node of its segment it is coupled to (empty: none)
+
+
+class _Owners(NamedTuple):
+    """Which rank does what, over the whole plan's unknowns, chain nodes and leaves (``ShardedKktPlan.__init__``)."""
+    member: np.ndarray       # [world, nu] bool: the unknown is part of the rank's local system
+    urank: np.ndarray        # [nu] the rank that eliminates a leaf / chain unknown (-1: border)
+    owner: np.ndarray        # [nu] the rank that supplies a border unknown's diagonal and right-hand side
+    red_pos: np.ndarray      # [nu] position in the reduced system (-1: none)
+    chain_rank: np.ndarray   # [n_chain]
+    leaf_rank: np.ndarray    # [n_leaf]
 
 
 def shard_cuts(engine, shard_plan):
@@ -89,14 +102,14 @@ class ShardedKktPlan:
             raise ValueError("ends must be 'chain' or 'border'")
         self.ends = ends
         self.world = W = shard_plan.world
-        ineq_rows = np.asarray(ineq_rows, dtype=np.int64)
         self.cuts, self.seg_rank = shard_cuts(engine, shard_plan)
-        P: dict = {}
         # the cut plan as one system (a single rank can run it: the reference of the tests, and the border's order)
-        self.whole = Tg = kkt.build_tables(engine, ineq_rows, fixed_v, row_scale, group, cuts=self.cuts, _parts=P,
-                                           _layout_only=not whole_entries)
-        cls, blk, nu, nv, n = P["cls"], P["blk"], P["nu"], P["nv"], P["n"]
-        self.nu = nu
+        nlp = kkt.classify(engine, ineq_rows, fixed_v, group, self.cuts)
+        S, Lg = nlp.system, kkt.layout(nlp.system)
+        self.whole = Tg = kkt.make_tables(Lg, kkt.entries_of_nlp(Lg, nlp, row_scale) if whole_entries
+                                          else kkt.entries_from_list(Lg, kkt.NO_ENTRIES, "positions"))
+        cls, blk, nv = S.cls, S.blk, S.nv
+        self.nu = nu = S.nu
         base_border = int(Tg.leaf_ptr[-1]) + int(Tg.chain_ptr[-1])
         self.border = Bg = Tg.perm[base_border:]                 # border unknowns in the reduced system's order
         self.nb_red = len(Bg)
@@ -117,24 +130,21 @@ class ShardedKktPlan:
         member[:, is_border] = True
         remap = [[] for _ in range(W)]      # per rank: (unknowns of a cut node, chain node that stands for it in the rank's segment)
         for ip, (c, sr) in enumerate(zip(self.cuts, self.seg_rank)):
-            mp = P["maps"][ip]
-            cut_boundaries = np.nonzero(mp[4])[0]
+            mp = nlp.maps[ip]
+            cut_boundaries = np.nonzero(mp.is_cut)[0]
             for j, node in enumerate(c):
-                u = np.nonzero(is_border & (P["u_phase"] == ip) & (P["u_node"] == node))[0]
+                u = np.nonzero(is_border & (nlp.u_phase == ip) & (nlp.u_node == node))[0]
                 owner[u] = sr[j + 1]
                 member[:, u] = False
                 member[sr[j], u] = True
                 member[sr[j + 1], u] = True
-                g_end = int(P["chain_base"][ip] + mp[5][cut_boundaries[j]])   # last node of the segment on its left ...
+                g_end = int(nlp.chain_base[ip] + mp.chain_id[cut_boundaries[j]])   # last node of the segment on its left ...
                 remap[sr[j]].append((u, g_end))
                 remap[sr[j + 1]].append((u, g_end + 1))                        # ... first node of the one on its right
         for r in range(W):
             member[r, urank == r] = True
         # ---- entries and the rank whose kernels write each entry's source ----------------------------------------------
-        eu, ev, ekind, eidx, ecoef = kkt.natural_entries(n, nv, P["hr"], P["hc"], P["jr"], P["jc"], row_scale, ineq_rows)
-        fixed = P["fixed"]
-        keep = ~(fixed[eu] | fixed[ev])
-        eu, ev, ekind, eidx, ecoef = eu[keep], ev[keep], ekind[keep], eidx[keep], ecoef[keep]
+        eu, ev, ekind, eidx, ecoef = kkt.natural_entries(nlp, row_scale)
         oG, oH = shard_plan.num_c, shard_plan.num_c + shard_plan.nnz_G
         pos_owner = np.full(oH + shard_plan.nnz_H, -1, np.int64)      # -1: written by the tail kernel (every rank has it)
         for r in range(W):
@@ -161,25 +171,21 @@ class ShardedKktPlan:
             bad = int(erank[np.nonzero((so >= 0) & (so != erank))[0][0]])
             raise RuntimeError(f"rank {bad}: a KKT entry of its blocks is written by another rank's tiles")
         self.ranks: list[RankTables] = []
+        who = _Owners(member, urank, owner, red_pos, chain_rank, leaf_rank)
         for r in range(W):
             if only is not None and r not in only:
                 self.ranks.append(None)
                 continue
             sel = erank == r
-            self.ranks.append(self._local(r, P, Tg, member[r], urank, owner, red_pos, chain_rank, leaf_rank,
-                                          (eu[sel], ev[sel], ekind[sel], eidx[sel], ecoef[sel]), positions,
+            self.ranks.append(self._local(r, S, who, (eu[sel], ev[sel], ekind[sel], eidx[sel], ecoef[sel]), positions,
                                           remap[r] if ends == "chain" else []))
         # ---- the reduced system: all border unknowns, dense, its entries arrive as the ranks' Schur complements --------
-        nr = self.nb_red
-        z = np.zeros(nr, np.int64)
-        e0 = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0))
-        self.reduced = kkt._finish(positions, 0, 0, nr, 0, 0, np.full(nr, BORDER, np.int8), z.copy(), z.copy(), z.copy(),
-                                   np.arange(nr, dtype=np.int64), np.zeros(nr, bool), np.zeros(nr, bool), 0, 0,
-                                   np.zeros(1, np.int64), np.zeros(0, np.int64), None, None, None, None, None, None,
-                                   entries=e0, n_primal=int(np.sum(Bg < nv)), n_dual=int(np.sum(Bg >= nv)))
+        self.reduced = kkt.system_tables(kkt.border_system(self.nb_red, int(np.sum(Bg < nv)), int(np.sum(Bg >= nv))),
+                                         kkt.NO_ENTRIES, positions)
 
-    def _local(self, r, P, Tg, member, urank, owner, red_pos, chain_rank, leaf_rank, entries, positions, remap) -> RankTables:
-        cls, blk = P["cls"], P["blk"]
+    def _local(self, r, S: kkt.Classified, who: _Owners, entries, positions, remap) -> RankTables:
+        """Rank r's part of the whole plan's system ``S`` as a classified system of its own, through the same stages."""
+        cls, blk, member, red_pos, chain_rank = S.cls, S.blk, who.member[r], who.red_pos, who.chain_rank
         if remap:                                   # the rank's shared nodes: chain nodes of its own segments
             cls, blk = cls.copy(), blk.copy()
             for u, gid in remap:
@@ -189,33 +195,32 @@ class ShardedKktPlan:
         g2l[univ] = np.arange(len(univ))
         # own chain segments and leaves, renumbered consecutively in the whole plan's order
         my_chain = np.nonzero(chain_rank == r)[0]
-        chain_l = np.full(Tg.n_chain, -1, np.int64)
+        chain_l = np.full(S.n_chain, -1, np.int64)
         chain_l[my_chain] = np.arange(len(my_chain))
-        my_leaf = np.nonzero(leaf_rank == r)[0]
-        leaf_l = np.full(Tg.n_leaf, -1, np.int64)
+        my_leaf = np.nonzero(who.leaf_rank == r)[0]
+        leaf_l = np.full(S.n_leaf, -1, np.int64)
         leaf_l[my_leaf] = np.arange(len(my_leaf))
-        seg = [(int(a), int(b)) for a, b in zip(Tg.chain_phase_ptr[:-1], Tg.chain_phase_ptr[1:]) if chain_rank[a] == r]
+        seg = [(int(a), int(b)) for a, b in zip(S.chain_phase_ptr[:-1], S.chain_phase_ptr[1:]) if chain_rank[a] == r]
         seg_ptr = np.concatenate([[0], np.cumsum([b - a for a, b in seg])]).astype(np.int64)
-        leaf_left = chain_l[Tg.leaf_left[my_leaf]] if len(my_leaf) else np.zeros(0, np.int64)
+        leaf_left = chain_l[S.leaf_left[my_leaf]] if len(my_leaf) else np.zeros(0, np.int64)
         c_l = cls[univ]
         b_l = np.zeros(len(univ), np.int64)
         b_l[c_l == LEAF] = leaf_l[blk[univ][c_l == LEAF]]
         b_l[c_l == CHAIN] = chain_l[blk[univ][c_l == CHAIN]]
         assert np.all(b_l >= 0) and np.all(leaf_left >= 0)
-        shared = P["cls"][univ] == BORDER           # (by the whole plan's classes: the NLP's border and the cut nodes)
-        own = (urank[univ] == r) | (shared & (owner[univ] == r))
+        shared = S.cls[univ] == BORDER              # (by the whole plan's classes: the NLP's border and the cut nodes)
+        own = (who.urank[univ] == r) | (shared & (who.owner[univ] == r))
         chain_export = None
         if remap:
             chain_export = np.zeros(len(my_chain), np.uint8)
             chain_export[chain_l[[gid for _, gid in remap]]] = 1
         eu, ev, ekind, eidx, ecoef = entries
-        nul = len(univ)
-        T = kkt._finish(positions, 0, 0, nul, 0, 0, c_l.astype(np.int8), b_l, P["key_node"][univ], P["key_kind"][univ],
-                        np.arange(nul, dtype=np.int64), P["dual"][univ], P["fixed"][univ] & own, len(my_leaf), len(my_chain),
-                        seg_ptr, leaf_left, None, None, None, None, None, None,
-                        entries=(g2l[eu], g2l[ev], ekind, eidx, ecoef),
-                        n_primal=int(np.sum(own & ~P["dual"][univ])), n_dual=int(np.sum(own & P["dual"][univ])),
-                        chain_export=chain_export)
+        dual = S.dual[univ]
+        local = kkt.Classified(nu=len(univ), nv=0, cls=c_l.astype(np.int8), blk=b_l, key_node=S.key_node[univ],
+                               key_kind=S.key_kind[univ], dual=dual, fixed=S.fixed[univ] & own, n_leaf=len(my_leaf),
+                               n_chain=len(my_chain), chain_phase_ptr=seg_ptr, leaf_left=leaf_left,
+                               n_primal=int(np.sum(own & ~dual)), n_dual=int(np.sum(own & dual)), chain_export=chain_export)
+        T = kkt.system_tables(local, (g2l[eu], g2l[ev], ekind, eidx, ecoef), positions)
         base_chain = int(T.leaf_ptr[-1])
         base_border = base_chain + int(T.chain_ptr[-1])
         border_red = red_pos[univ[T.perm[base_border:]]]

@@ -83,6 +83,25 @@ def test_a_rank_holds_its_share_and_a_border_that_does_not_grow_with_the_world(b
     eng.close()
 
 
+@pytest.mark.parametrize("name,kw,world", [CASES[0], CASES[2]])
+def test_the_whole_plan_without_entry_tables_keeps_order_and_layout(built, name, kw, world):
+    """``whole_entries=False`` (the default): ``plan.whole`` is the cut plan's block order, value-buffer layout and
+    diagonal positions exactly as with its entry tables, and the entry tables themselves are empty."""
+    eng, _, _, _, ineq, fixed, sc, _ = kkt_case(name, kw)
+    sp = ShardPlan(eng, world)
+    bare = kkt_sharded.ShardedKktPlan(eng, ineq, fixed, sc, sp, ends="chain", whole_entries=False).whole
+    full = kkt_sharded.ShardedKktPlan(eng, ineq, fixed, sc, sp, ends="chain", whole_entries=True).whole
+    for f in ("nu", "nv", "n_leaf", "n_chain", "n_phase", "nb", "n_primal", "n_dual", "border_off", "total_vals"):
+        assert getattr(bare, f) == getattr(full, f), f
+    for f in ("perm", "leaf_ptr", "chain_ptr", "chain_phase_ptr", "leaf_left", "leafA_off", "leafS_off", "chainD_off",
+              "chainS_off", "diag_pos", "fixed"):
+        a, b = getattr(bare, f), getattr(full, f)
+        assert np.array_equal(a, b) and a.dtype == b.dtype, f
+    assert len(bare.dst) == len(bare.src_kind) == len(bare.mv_col) == 0
+    assert len(full.dst) > 0 and len(full.src_kind) > 0 and len(full.mv_col) > 0
+    eng.close()
+
+
 @pytest.mark.parametrize("name,kw,world", CASES)
 def test_shared_nodes_as_chain_ends_tables_reduce_to_the_whole_system(built, name, kw, world):
     """``ends="chain"`` (the default): a rank keeps the nodes it shares as the first / last node of its chain segment and
