@@ -529,6 +529,33 @@ int pc_solution_sample(pc_solution* sol, int phase, const double* t, int64_t n_t
 int pc_solution_sample_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_y, double* d_dy,
                               double* d_u, double* d_f);
 
+/* ---- costates and the Hamiltonian (no reference counterpart) ----
+ * lam: the scaled multipliers of all n_lam = num_c constraint rows (the solver's mult_g / pycollo's lam_g).  tabA: for
+ * every listed order n the (n - 1) x n integration table A(n), row-major, concatenated in the order of `orders`.
+ * With Lam = W lam / w (the handle's constraint and objective scaling, read by this call), h_k the width of section k
+ * in tau and omega_j = sum_{k contains j} h_k A_k[n_k - 2][pos_k(j)]:
+ *   p_a(j) = ( sum_{k contains j} h_k sum_r Lam_a[s_k + r] A_k[r][pos_k(j)] ) / omega_j     (omega_j = 0, the Radau
+ *            phase-final node: p_a = Lam_a[N - 2] and H = NaN)
+ *   nu_m = -Lam_q[m],   H(j) = sum_a p_a f_a + sum_m nu_m g_m
+ * Between the nodes p is the degree n_k - 1 interpolant of the section's node values (Legendre coefficients, laid out
+ * like the controls'), and H(t) is formed from p(t) and f, g at the interpolated (y(t), u(t)).  Runs pc_sol_costate_p<i>
+ * on the handle's stream and synchronises; may be called again with other multipliers. */
+int pc_solution_set_multipliers(pc_solution* sol, const double* lam, int64_t n_lam, int n_orders, const int32_t* orders,
+                                const double* tabA);
+/* the same from a device vector, read in place */
+int pc_solution_set_multipliers_device(pc_solution* sol, const double* d_lam, int64_t n_lam, int n_orders, const int32_t* orders,
+                                       const double* tabA);
+/* p [n_y][N], H [N], nu [n_q]; NULL: skipped.  These four fail until multipliers were set. */
+int pc_solution_costate_nodes(pc_solution* sol, int phase, double* p, double* H, double* nu);
+/* p_coef [n_y][N + K - 1] */
+int pc_solution_costate_coefficients(pc_solution* sol, int phase, double* p_coef);
+/* p [n_y][n_t] and H [n_t] at the queries of pc_solution_sample (same flags, same range handling).  Host pointers;
+ * synchronises. */
+int pc_solution_sample_costate(pc_solution* sol, int phase, const double* t, int64_t n_t, int flags, double* p, double* H);
+/* the same with device pointers, queued on the handle's stream; does not synchronise */
+int pc_solution_sample_costate_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_p,
+                                      double* d_H);
+
 /* timing of the last n pc_eval_all_device launches is measured by the caller with HIP events on the
  * stream it passed; this returns the stream the handle owns (hipStream_t) */
 void* pc_stream(pc_handle* h);

@@ -221,7 +221,12 @@ def _phase_struct(pm: PhaseModel, model: Model | None = None) -> str:
     fbody = [f"    constexpr double {k} = {float(val)!r};" for k, val in pm.consts]
     fbody += _emit_block(v_in, [(f"F[{i}]", e) for i, e in enumerate(pm.f)], "w")
     lines += ["  __device__ static __forceinline__ void eval_f(const double* __restrict__ v, double* __restrict__ F) {",
-              "    (void)v; (void)F;"] + fbody + ["  }", "};", ""]
+              "    (void)v; (void)F;"] + fbody + ["  }"]
+    # state equations and integrands (the Hamiltonian of the costate kernels, pc_solution.hpp)
+    fg = [(f"F[{i}]", e) for i, e in enumerate(pm.f)] + [(f"Gq[{i}]", e) for i, e in enumerate(pm.g)]
+    lines += ["  __device__ static __forceinline__ void eval_fg(const double* __restrict__ v, double* __restrict__ F,",
+              "      double* __restrict__ Gq) {", "    (void)v; (void)F; (void)Gq;"]
+    lines += cdecl + _emit_block(v_in, fg, "w") + ["  }", "};", ""]
     assert nfn >= 0 and nv >= 0
     return "\n".join(lines)
 

@@ -335,4 +335,37 @@ struct PcSolSampleArgs {
   double scal[PC_MAX_SCAL];
 };
 
+// Arguments of the costate kernels (pc_solution.hpp, "costates").  lam is the scaled multiplier vector of the whole
+// NLP, read in place: defect row r of state a of this phase is lam[c_off + a (N - 1) + r], integral row m is
+// lam[c_int_off + m].  The A tables are the (n - 1) x n integration tables of the orders in use, row-major, order n at
+// offA[n]; scal's Wd / Wi entries and wJ are the constraint and objective scaling the multipliers belong to.
+struct PcSolCostateArgs {
+  const double* x;          // [num_x] scaled NLP point
+  const double* lam;        // [num_c] scaled multipliers
+  const int32_t* tile_k0;   // [n_tiles+1] the fit kernel's tiles
+  const int32_t* lane0;     // [K]
+  const int32_t* sec_s;     // [K+1]
+  const double* sec_tau;    // [K+1] tau at the section boundaries: h_k = sec_tau[k+1] - sec_tau[k]
+  const double* tabA;       // per order n: (n-1) x n integration table
+  const double* tabU;       // per order n: n x n, node values -> Legendre coefficients through all n nodes
+  double* node_p;           // [NY][N] costates
+  double* node_H;           // [N] Hamiltonian (NaN at a node without quadrature weight)
+  double* coef_p;           // [NY][NC]
+  double* nu;               // [NQ] integrand weights of the Hamiltonian
+  int64_t x_off, s_off, c_off, c_int_off;
+  double wJ;
+  int32_t N, K, NC, tab_total, a_total, reserved;
+  int32_t offC[PC_MAX_ORDER + 1];
+  int32_t offA[PC_MAX_ORDER + 1];
+  double scal[PC_MAX_SCAL];
+};
+
+struct PcSolCostateSampleArgs {
+  PcSolSampleArgs s;        // the queries, the flags and the trajectory's polynomials (its outputs are not used)
+  const double* coef_p;     // [NY][NC]
+  const double* nu;         // [NQ]
+  double* out_p;            // [NY][Q]
+  double* out_H;            // [Q]
+};
+
 #endif  // PC_ARGS_H

@@ -128,15 +128,19 @@ __device__ __forceinline__ void sol_fit(const PcSolFitArgs& A) {
 // the section's coefficients from high to low degree -- one pass feeds the Clenshaw recurrences of ydot and of its
 // integral.  Outputs are variable-major [var][Q]: neighbouring lanes write neighbouring doubles.
 // ---------------------------------------------------------------------------------------------
+// where a query lands
+struct SolSpot {
+  int k, sk, n;        // section, its first node, its nodes
+  double c, w;         // section variable in [-1, 1], section width in tau
+  double stretch;
+  int64_t off;         // the section's first coefficient
+};
+
+// false: the query is outside the phase (or NaN) and is not extrapolated -- every output of the lane is NaN
 template <class M>
-__device__ __forceinline__ void sol_sample(const PcSolSampleArgs& A) {
-  using St = S<M>;
-  constexpr int NY = St::NY, NU = St::NU;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.Q) return;
-  const double* sc = A.scal;
+__device__ __forceinline__ bool sol_locate(const PcSolSampleArgs& A, int64_t i, SolSpot& s) {
   double t0, tF;
-  sol_times<M>(A.x, sc, A.x_off, A.N, A.t_fixed, t0, tF);
+  sol_times<M>(A.x, A.scal, A.x_off, A.N, A.t_fixed, t0, tF);
   const double stretch = 0.5 * (tF - t0), shift = 0.5 * (t0 + tF);
   const double q = A.t[i];
   double tau;
@@ -151,8 +155,70 @@ __device__ __forceinline__ void sol_sample(const PcSolSampleArgs& A) {
     inside = fabs(tau) <= 1.0 + PC_SOL_END_SLACK;
     if (inside) tau = fmin(1.0, fmax(-1.0, tau));
   }
-  const double nan = __builtin_nan("");
-  if (!(inside || ((A.flags & PC_SOL_EXTRAPOLATE) && tau == tau))) {
+  if (!(inside || ((A.flags & PC_SOL_EXTRAPOLATE) && tau == tau))) return false;
+  // the last boundary <= tau, kept inside [0, K - 1]
+  int lo = 0, hi = A.K;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (A.sec_tau[mid] <= tau) lo = mid; else hi = mid;
+  }
+  s.k = lo;
+  s.sk = A.sec_s[lo];
+  s.n = A.sec_s[lo + 1] - s.sk + 1;
+  const double ta = A.sec_tau[lo];
+  s.w = A.sec_tau[lo + 1] - ta;
+  s.c = 2.0 * (tau - ta) / s.w - 1.0;
+  s.stretch = stretch;
+  s.off = (int64_t)s.sk + lo;
+  return true;
+}
+
+// state a at the spot (the integrated form) and, in d, its derivative
+__device__ __forceinline__ double sol_state(const PcSolSampleArgs& A, const SolSpot& s, int a, double& d) {
+  const double* cf = A.coef_dy + (int64_t)a * A.NC + s.off;
+  const double c = s.c;
+  // j = n .. 0: b_j = a_(j-1) / (2j - 1) - a_(j+1) / (2j + 3) are the coefficients of int_{-1}^{c} ydot
+  // (b_0 = a_0 - a_1 / 3); ydot's own Clenshaw step j uses a_j
+  double a_hi = 0.0, a_mid = 0.0;
+  double y1 = 0.0, y2 = 0.0, d1 = 0.0, d2 = 0.0;
+  for (int j = s.n; j >= 0; --j) {
+    const double a_lo = j >= 1 ? cf[j - 1] : 0.0;
+    const double bj = (j >= 1 ? a_lo / (double)(2 * j - 1) : a_mid) - a_hi / (double)(2 * j + 3);
+    const double al = (double)(2 * j + 1) / (double)(j + 1) * c, be = (double)(j + 1) / (double)(j + 2);
+    const double yn = bj + (al * y1 - be * y2);
+    y2 = y1;
+    y1 = yn;
+    const double dn = a_mid + (al * d1 - be * d2);
+    d2 = d1;
+    d1 = dn;
+    a_hi = a_mid;
+    a_mid = a_lo;
+  }
+  d = d1;
+  return A.node_y[(int64_t)a * A.N + s.sk] + s.stretch * ((0.5 * s.w) * y1);
+}
+
+// sum_j cf[j] P_j(c), j < n (Clenshaw): the controls, the costates
+__device__ __forceinline__ double sol_legendre(const double* cf, int n, double c) {
+  double u1 = 0.0, u2 = 0.0;
+  for (int j = n - 1; j >= 0; --j) {
+    const double al = (double)(2 * j + 1) / (double)(j + 1) * c, be = (double)(j + 1) / (double)(j + 2);
+    const double un = cf[j] + (al * u1 - be * u2);
+    u2 = u1;
+    u1 = un;
+  }
+  return u1;
+}
+
+template <class M>
+__device__ __forceinline__ void sol_sample(const PcSolSampleArgs& A) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NU = St::NU;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.Q) return;
+  SolSpot s;
+  if (!sol_locate<M>(A, i, s)) {
+    const double nan = __builtin_nan("");
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
       if (A.out_y) A.out_y[(int64_t)a * A.Q + i] = nan;
@@ -164,72 +230,199 @@ __device__ __forceinline__ void sol_sample(const PcSolSampleArgs& A) {
     });
     return;
   }
-  // the last boundary <= tau, kept inside [0, K - 1]
-  int lo = 0, hi = A.K;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (A.sec_tau[mid] <= tau) lo = mid; else hi = mid;
-  }
-  const int k = lo;
-  const int sk = A.sec_s[k], n = A.sec_s[k + 1] - sk + 1;
-  const double ta = A.sec_tau[k], w = A.sec_tau[k + 1] - ta;
-  const double c = 2.0 * (tau - ta) / w - 1.0;
-  const int64_t off = (int64_t)sk + k;
   double v[St::NV > 0 ? St::NV : 1], F[NY > 0 ? NY : 1];
   static_for<0, NY>([&](auto a_) {
     constexpr int a = decltype(a_)::value;
-    const double* cf = A.coef_dy + (int64_t)a * A.NC + off;
-    // j = n .. 0: b_j = a_(j-1) / (2j - 1) - a_(j+1) / (2j + 3) are the coefficients of int_{-1}^{c} ydot
-    // (b_0 = a_0 - a_1 / 3); ydot's own Clenshaw step j uses a_j
-    double a_hi = 0.0, a_mid = 0.0;
-    double y1 = 0.0, y2 = 0.0, d1 = 0.0, d2 = 0.0;
-    for (int j = n; j >= 0; --j) {
-      const double a_lo = j >= 1 ? cf[j - 1] : 0.0;
-      const double bj = (j >= 1 ? a_lo / (double)(2 * j - 1) : a_mid) - a_hi / (double)(2 * j + 3);
-      const double al = (double)(2 * j + 1) / (double)(j + 1) * c, be = (double)(j + 1) / (double)(j + 2);
-      const double yn = bj + (al * y1 - be * y2);
-      y2 = y1;
-      y1 = yn;
-      const double dn = a_mid + (al * d1 - be * d2);
-      d2 = d1;
-      d1 = dn;
-      a_hi = a_mid;
-      a_mid = a_lo;
-    }
-    const double y = A.node_y[(int64_t)a * A.N + sk] + stretch * ((0.5 * w) * y1);
+    double d;
+    const double y = sol_state(A, s, a, d);
     v[a] = y;
     if (A.out_y) A.out_y[(int64_t)a * A.Q + i] = y;
-    if (A.out_dy) A.out_dy[(int64_t)a * A.Q + i] = d1;
+    if (A.out_dy) A.out_dy[(int64_t)a * A.Q + i] = d;
   });
   static_for<0, NU>([&](auto b_) {
     constexpr int b = decltype(b_)::value;
-    const double* cf = A.coef_u + (int64_t)b * A.NC + off;
-    double u1 = 0.0, u2 = 0.0;
-    for (int j = n - 1; j >= 0; --j) {
-      const double al = (double)(2 * j + 1) / (double)(j + 1) * c, be = (double)(j + 1) / (double)(j + 2);
-      const double un = cf[j] + (al * u1 - be * u2);
-      u2 = u1;
-      u1 = un;
-    }
-    v[NY + b] = u1;
-    if (A.out_u) A.out_u[(int64_t)b * A.Q + i] = u1;
+    const double u = sol_legendre(A.coef_u + (int64_t)b * A.NC + s.off, s.n, s.c);
+    v[NY + b] = u;
+    if (A.out_u) A.out_u[(int64_t)b * A.Q + i] = u;
   });
   if (A.out_f) {
-    sol_params<M>(A.x, sc, A.x_off, A.s_off, A.N, v);
+    sol_params<M>(A.x, A.scal, A.x_off, A.s_off, A.N, v);
     M::eval_f(v, F);
     static_for<0, NY>([&](auto a_) { A.out_f[(int64_t) decltype(a_)::value * A.Q + i] = F[decltype(a_)::value]; });
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Costates and the Hamiltonian.  Lam = W lam~ / w are the multipliers of the unscaled rows for the
+// unscaled objective.  Per node j, over the one or two sections k that contain it (lower section first, rows ascending,
+// one division at the end):
+//   omega_j = sum_k h_k A_k[n_k - 2][pos_k(j)]
+//   p_a(j)  = ( sum_k h_k sum_r Lam_a[s_k + r] A_k[r][pos_k(j)] ) / omega_j;   omega_j == 0 (the Radau phase-final node,
+//             an exact zero of the table): p_a = Lam_a[N - 2], H = NaN
+//   nu_m    = -Lam_q[m];   H(j) = sum_a p_a f_a + sum_m nu_m g_m at the node's (y, u, q, t, s)
+//
+// pc_sol_costate_p<i>: the tiles and lanes of pc_sol_fit.  The workgroup stages the A and C_u tables and the rows of
+// Lam its nodes need (those of its sections and of the two neighbour sections its end lanes reach into); both lanes of
+// a shared node run the same sums on the same operands, the section the node opens writes it.  Then lane j of a
+// section contracts row j of C_u with the section's costates: coefficient j.
+// ---------------------------------------------------------------------------------------------
+#define PC_SOL_LAM_ROWS(TB) ((TB) + 2 * PC_MAX_ORDER)   // staged rows of one state: <= TB - 1 own + 2 x 19 neighbour rows
+
+template <class M>
+__device__ __forceinline__ void sol_costate(const PcSolCostateArgs& A) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NZ = St::NZ, NQ = St::NQ;
+  constexpr int NY1 = NY > 0 ? NY : 1, NQ1 = NQ > 0 ? NQ : 1;
+  extern __shared__ double smem[];
+  const int tid = threadIdx.x, TB = blockDim.x, LW = PC_SOL_LAM_ROWS(TB);
+  double* s_U = smem;
+  double* s_A = s_U + A.tab_total;
+  double* s_lam = s_A + A.a_total;                   // [NY][LW] Lam of rows r_lo ..
+  double* s_p = s_lam + NY1 * LW;                    // [NY][TB]
+  int* s_sec = reinterpret_cast<int*>(s_p + NY1 * TB);   // [TB] section of every lane
+  const int k0 = A.tile_k0[blockIdx.x], k1 = A.tile_k0[blockIdx.x + 1];
+  const double* sc = A.scal;
+  for (int i = tid; i < A.tab_total; i += TB) s_U[i] = A.tabU[i];
+  for (int i = tid; i < A.a_total; i += TB) s_A[i] = A.tabA[i];
+  // rows of the tile's sections and of the sections before and after it
+  const int r_lo = A.sec_s[k0 > 0 ? k0 - 1 : 0], r_hi = A.sec_s[k1 < A.K ? k1 + 1 : A.K];
+  static_for<0, NY>([&](auto a_) {
+    constexpr int a = decltype(a_)::value;
+    const double* la = A.lam + A.c_off + (int64_t)a * (A.N - 1) + r_lo;
+    for (int i = tid; i < r_hi - r_lo && i < LW; i += TB) s_lam[a * LW + i] = sc[St::O_WD + a] * la[i] / A.wJ;
+  });
+  s_sec[tid] = -1;
+  __syncthreads();
+  for (int k = k0 + tid; k < k1; k += TB) {
+    const int n = A.sec_s[k + 1] - A.sec_s[k] + 1, l0 = A.lane0[k];
+    for (int j = 0; j < n; ++j)
+      if (l0 + j < TB) s_sec[l0 + j] = k;
+  }
+  __syncthreads();
+  const int k = s_sec[tid];
+  const bool active = k >= 0;
+  int n = 2, j = 0, l0 = 0, sk = 0;
+  if (active) {
+    sk = A.sec_s[k];
+    n = A.sec_s[k + 1] - sk + 1;
+    l0 = A.lane0[k];
+    j = tid - l0;
+    const int node = sk + j;
+    // the sections of the node: [ka, kb], positions pa (in ka) and 0 (in kb > ka)
+    int ka = k, pa = j, kb = k;
+    if (j == 0 && k > 0) { ka = k - 1; pa = sk - A.sec_s[k - 1]; }
+    if (j == n - 1 && k < A.K - 1) kb = k + 1;
+    double omega = 0.0, num[NY1];
+    static_for<0, NY>([&](auto a_) { num[decltype(a_)::value] = 0.0; });
+    for (int kk = ka; kk <= kb; ++kk) {
+      const int s0 = A.sec_s[kk], nn = A.sec_s[kk + 1] - s0 + 1, pos = kk == ka ? pa : 0;
+      const double h = A.sec_tau[kk + 1] - A.sec_tau[kk];
+      const double* At = s_A + A.offA[nn] + pos;
+      omega += h * At[(nn - 2) * nn];
+      static_for<0, NY>([&](auto a_) {
+        constexpr int a = decltype(a_)::value;
+        const double* la = s_lam + a * LW + (s0 - r_lo);
+        double acc = 0.0;
+        for (int r = 0; r < nn - 1; ++r) acc += la[r] * At[r * nn];
+        num[a] += h * acc;
+      });
+    }
+    double v[St::NV > 0 ? St::NV : 1], F[NY1], G[NQ1], p[NY1];
+    sol_params<M>(A.x, sc, A.x_off, A.s_off, A.N, v);
+    static_for<0, NZ>([&](auto b_) {
+      constexpr int b = decltype(b_)::value;
+      v[b] = sc[St::O_VZ + b] * A.x[A.x_off + (int64_t)b * A.N + node] + sc[St::O_RZ + b];
+    });
+    M::eval_fg(v, F, G);
+    const bool weighted = !(node == A.N - 1 && omega == 0.0);   // (the tile of node N - 1 stages row N - 2)
+    double H = 0.0;
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      p[a] = weighted ? num[a] / omega : s_lam[a * LW + (A.N - 2 - r_lo)];
+      H += p[a] * F[a];
+    });
+    static_for<0, NQ>([&](auto m_) {
+      constexpr int m = decltype(m_)::value;
+      const double nu = -(sc[St::O_WI + m] * A.lam[A.c_int_off + m] / A.wJ);
+      H += nu * G[m];
+      if (blockIdx.x == 0 && tid == 0) A.nu[m] = nu;
+    });
+    const bool owner = j < n - 1 || k == A.K - 1;
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      s_p[a * TB + tid] = p[a];
+      if (owner) A.node_p[(int64_t)a * A.N + node] = p[a];
+    });
+    if (owner) A.node_H[node] = weighted ? H : __builtin_nan("");
+  }
+  __syncthreads();
+  if (active) {
+    const double* Ur = s_U + A.offC[n] + j * n;
+    const int64_t slot = (int64_t)sk + k + j;
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      double acc = 0.0;
+      for (int i = 0; i < n; ++i) acc += Ur[i] * s_p[a * TB + l0 + i];
+      A.coef_p[(int64_t)a * A.NC + slot] = acc;
+    });
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// pc_sol_sample_costate_p<i>: one lane per query, located as in pc_sol_sample.  p(t) is the section's interpolant of
+// the node costates; H(t) = sum_a p_a(t) f_a + sum_m nu_m g_m with f, g at the interpolated (y(t), u(t)).
+// ---------------------------------------------------------------------------------------------
+template <class M>
+__device__ __forceinline__ void sol_sample_costate(const PcSolCostateSampleArgs& B) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NU = St::NU, NQ = St::NQ;
+  const PcSolSampleArgs& A = B.s;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.Q) return;
+  SolSpot s;
+  if (!sol_locate<M>(A, i, s)) {
+    const double nan = __builtin_nan("");
+    static_for<0, NY>([&](auto a_) { B.out_p[(int64_t) decltype(a_)::value * A.Q + i] = nan; });
+    B.out_H[i] = nan;
+    return;
+  }
+  double v[St::NV > 0 ? St::NV : 1], F[NY > 0 ? NY : 1], G[NQ > 0 ? NQ : 1];
+  static_for<0, NY>([&](auto a_) {
+    double d;
+    v[decltype(a_)::value] = sol_state(A, s, decltype(a_)::value, d);
+  });
+  static_for<0, NU>([&](auto b_) {
+    constexpr int b = decltype(b_)::value;
+    v[NY + b] = sol_legendre(A.coef_u + (int64_t)b * A.NC + s.off, s.n, s.c);
+  });
+  sol_params<M>(A.x, A.scal, A.x_off, A.s_off, A.N, v);
+  M::eval_fg(v, F, G);
+  double H = 0.0;
+  static_for<0, NY>([&](auto a_) {
+    constexpr int a = decltype(a_)::value;
+    const double p = sol_legendre(B.coef_p + (int64_t)a * A.NC + s.off, s.n, s.c);
+    B.out_p[(int64_t)a * A.Q + i] = p;
+    H += p * F[a];
+  });
+  static_for<0, NQ>([&](auto m_) { H += B.nu[decltype(m_)::value] * G[decltype(m_)::value]; });
+  B.out_H[i] = H;
+}
+
 }  // namespace pc
 
-// the two entry points of phase I, instantiated by the generated source once per phase
+// the four entry points of phase I, instantiated by the generated source once per phase
 #define PC_SOL_ENTRY_POINTS(I)                                                                               \
   extern "C" __global__ void __launch_bounds__(256) pc_sol_fit_p##I(PcSolFitArgs a) {                        \
     pc::sol_fit<gen::Phase##I>(a);                                                                           \
   }                                                                                                          \
   extern "C" __global__ void __launch_bounds__(256) pc_sol_sample_p##I(PcSolSampleArgs a) {                  \
     pc::sol_sample<gen::Phase##I>(a);                                                                        \
+  }                                                                                                          \
+  extern "C" __global__ void __launch_bounds__(256) pc_sol_costate_p##I(PcSolCostateArgs a) {                \
+    pc::sol_costate<gen::Phase##I>(a);                                                                       \
+  }                                                                                                          \
+  extern "C" __global__ void __launch_bounds__(256) pc_sol_sample_costate_p##I(PcSolCostateSampleArgs a) {   \
+    pc::sol_sample_costate<gen::Phase##I>(a);                                                                \
   }
 
 #endif  // PC_SOLUTION_HPP

@@ -5,18 +5,25 @@
 // A solution owns a copy of the point it was made from and everything derived from it; it reads the handle's scaling
 // constants once, at creation, and launches on the handle's stream.  The handle's staged point, its callback caches and
 // its outputs are not touched: an evaluation after any of these calls returns what it returned before.
-#include "pc_solution_plan.hpp"
+//
+// Costates (pc_solution_set_multipliers): the index arithmetic is pc_costate_plan.hpp.  The multipliers belong to the
+// constraint and objective scaling the handle holds when they are set, which are read then.
+#include "pc_costate_plan.hpp"
 
 struct pc_solution {
   pc_handle* h = nullptr;
   DevBuf<double> d_x;
+  DevBuf<double> d_U;       // the C_u tables (the costate kernel forms its coefficients with them)
+  DevBuf<double> d_lam;     // a host multiplier vector's device copy
+  bool has_costate = false;
   struct Phase {
     pcs::FitPlan plan;
-    DevBuf<int32_t> sec_s;
+    DevBuf<int32_t> sec_s, tile_k0, lane0;
     DevBuf<double> sec_tau, node_t, node_y, node_u, node_f, coef_dy, coef_u;
-    hipFunction_t fn_sample = nullptr;
+    DevBuf<double> node_p, node_H, coef_p, nu;   // costates: allocated by pc_solution_set_multipliers
+    hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr;
     PcSolSampleArgs args;   // everything but the queries, the outputs and the flags
-    int NY = 0, NU = 0;
+    int NY = 0, NU = 0, NQ = 0;
   };
   std::vector<std::unique_ptr<Phase>> ph;
 };
@@ -28,11 +35,11 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
   pc_handle* h = s->h;
   auto& Q = h->Q;
   if (!tabD || !tabU || !tau) throw std::runtime_error("solution: null table");
-  DevBuf<double> d_D, d_U;
+  DevBuf<double> d_D;
   int32_t offC[PC_MAX_ORDER + 1];
   const int32_t tab_total = pcs::table_offsets(n_orders, orders, offC);
   d_D.upload(std::vector<double>(tabD, tabD + tab_total));
-  d_U.upload(std::vector<double>(tabU, tabU + tab_total));
+  s->d_U.upload(std::vector<double>(tabU, tabU + tab_total));
   size_t tau_off = 0;
   for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
     auto& P = Q.ph[ip];
@@ -40,15 +47,15 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     auto S = std::make_unique<pc_solution::Phase>();
     S->NY = P.n_y;
     S->NU = P.n_u;
+    S->NQ = P.n_q;
     S->plan = pcs::build_fit_plan(P.K, P.n_k.data(), n_orders, orders, P.n_y, P.n_u, 256, h->lds_limit);
     const pcs::FitPlan& F = S->plan;
     if (F.N != P.N) throw std::runtime_error("solution: the plan's node count differs from the handle's");
     if (D.scal_host.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
     const std::vector<double> edges = pcs::section_edges(F, tau + tau_off);
-    DevBuf<int32_t> d_tile, d_lane;
     DevBuf<double> d_tau;
-    d_tile.upload(F.tile_k0);
-    d_lane.upload(F.lane0);
+    S->tile_k0.upload(F.tile_k0);
+    S->lane0.upload(F.lane0);
     d_tau.upload(std::vector<double>(tau + tau_off, tau + tau_off + P.N));
     tau_off += (size_t)P.N;
     S->sec_s.upload(F.sec_s);
@@ -67,11 +74,11 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     std::memset(&a, 0, sizeof(a));
     a.x = s->d_x.p;
     a.tau = d_tau.p;
-    a.tile_k0 = d_tile.p;
-    a.lane0 = d_lane.p;
+    a.tile_k0 = S->tile_k0.p;
+    a.lane0 = S->lane0.p;
     a.sec_s = S->sec_s.p;
     a.tabD = d_D.p;
-    a.tabU = d_U.p;
+    a.tabU = s->d_U.p;
     a.node_t = S->node_t.p;
     a.node_y = S->node_y.p;
     a.node_u = S->node_u.p;
@@ -91,7 +98,7 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     size_t sz = sizeof(a);
     void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
     HIP_OK(hipModuleLaunchKernel(fn_fit, F.n_tiles(), 1, 1, F.TB, 1, 1, (unsigned)F.lds_bytes, h->stream, nullptr, cfg));
-    HIP_OK(hipStreamSynchronize(h->stream));   // the tile tables above are released on return
+    HIP_OK(hipStreamSynchronize(h->stream));   // the tables above are released on return
     PcSolSampleArgs& q = S->args;
     std::memset(&q, 0, sizeof(q));
     q.x = s->d_x.p;
@@ -129,6 +136,109 @@ void solution_launch_sample(pc_solution* s, int phase, const double* d_t, int64_
   HIP_OK(hipModuleLaunchKernel(S.fn_sample, (unsigned)pcs::sample_blocks(n_t, 256), 1, 1, 256, 1, 1, 0, s->h->stream, nullptr, cfg));
 }
 
+// the costates of every phase from the device vector d_lam (pc_sol_costate_p<i>), then the arguments of the sampling calls
+void solution_costate(pc_solution* s, const double* d_lam, int n_orders, const int32_t* orders, const double* tabA) {
+  pc_handle* h = s->h;
+  auto& Q = h->Q;
+  int32_t offA[PC_MAX_ORDER + 1];
+  const int32_t a_total = pcs::a_table_offsets(n_orders, orders, offA);
+  DevBuf<double> d_A;
+  d_A.upload(std::vector<double>(tabA, tabA + a_total));
+  for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
+    auto& P = Q.ph[ip];
+    auto& D = *h->pd[ip];
+    auto& S = *s->ph[ip];
+    const pcs::FitPlan& F = S.plan;
+    const pcs::CostatePlan C =
+        pcs::build_costate_plan(F, n_orders, orders, P.n_y, P.n_q, P.c_off, P.c_int_off, Q.num_c, h->lds_limit);
+    if (D.scal_host.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
+    const size_t ny = (size_t)std::max(1, P.n_y);
+    if (!S.node_p.p) {
+      S.node_p.alloc(ny * F.N);
+      S.node_H.alloc((size_t)F.N);
+      S.coef_p.alloc(ny * F.NC);
+      S.nu.alloc((size_t)std::max(1, P.n_q));
+    }
+    hipFunction_t fn = nullptr;
+    HIP_OK(find_fn(h, &fn, ("pc_sol_costate_p" + std::to_string(ip)).c_str()));
+    HIP_OK(find_fn(h, &S.fn_sample_costate, ("pc_sol_sample_costate_p" + std::to_string(ip)).c_str()));
+    PcSolCostateArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.x = s->d_x.p;
+    a.lam = d_lam;
+    a.tile_k0 = S.tile_k0.p;
+    a.lane0 = S.lane0.p;
+    a.sec_s = S.sec_s.p;
+    a.sec_tau = S.sec_tau.p;
+    a.tabA = d_A.p;
+    a.tabU = s->d_U.p;
+    a.node_p = S.node_p.p;
+    a.node_H = S.node_H.p;
+    a.coef_p = S.coef_p.p;
+    a.nu = S.nu.p;
+    a.x_off = P.x_off;
+    a.s_off = Q.s_off;
+    a.c_off = P.c_off;
+    a.c_int_off = P.c_int_off;
+    a.wJ = h->w_J;
+    a.N = F.N;
+    a.K = F.K;
+    a.NC = F.NC;
+    a.tab_total = F.tab_total;
+    a.a_total = a_total;
+    for (int i = 0; i <= PC_MAX_ORDER; ++i) {
+      a.offC[i] = F.offC[i];
+      a.offA[i] = C.offA[i];
+    }
+    // the variables are unscaled as the solution's node values were; the row scaling is the handle's of now
+    constexpr size_t n_scal = sizeof(a.scal) / sizeof(a.scal[0]);
+    for (size_t i = 0; i < n_scal; ++i) a.scal[i] = S.args.scal[i];
+    const size_t o_w = D.scal_host.size() - (size_t)(P.n_y + P.n_p + P.n_q);
+    for (size_t i = o_w; i < D.scal_host.size(); ++i) a.scal[i] = D.scal_host[i];
+    size_t sz = sizeof(a);
+    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+    HIP_OK(hipModuleLaunchKernel(fn, F.n_tiles(), 1, 1, F.TB, 1, 1, (unsigned)C.lds_bytes, h->stream, nullptr, cfg));
+  }
+  HIP_OK(hipStreamSynchronize(h->stream));   // d_A is released on return; a caller's device vector is free again
+  s->has_costate = true;
+}
+
+int solution_set_multipliers(pc_solution* s, const double* lam, int64_t n_lam, bool on_device, int n_orders, const int32_t* orders,
+                             const double* tabA) {
+  return guarded([&] {
+    if (!s) throw std::runtime_error("null solution");
+    require_device(s->h);
+    pcs::check_multiplier_args(lam, n_lam, s->h->Q.num_c, tabA, s->h->w_J);
+    HIP_OK(hipSetDevice(s->h->device));
+    const double* d_lam = lam;
+    if (!on_device) {
+      if (s->d_lam.n != (size_t)n_lam) s->d_lam.alloc((size_t)n_lam);
+      HIP_OK(hipMemcpyAsync(s->d_lam.p, lam, (size_t)n_lam * sizeof(double), hipMemcpyHostToDevice, s->h->stream));
+      d_lam = s->d_lam.p;
+    }
+    solution_costate(s, d_lam, n_orders, orders, tabA);
+  });
+}
+
+void solution_launch_sample_costate(pc_solution* s, int phase, const double* d_t, int64_t n_t, int flags, double* d_p, double* d_H) {
+  auto& S = *s->ph[phase];
+  if (n_t == 0) return;
+  PcSolCostateSampleArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.s = S.args;
+  a.s.t = d_t;
+  a.s.Q = n_t;
+  a.s.flags = flags;
+  a.coef_p = S.coef_p.p;
+  a.nu = S.nu.p;
+  a.out_p = d_p;
+  a.out_H = d_H;
+  size_t sz = sizeof(a);
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  HIP_OK(hipModuleLaunchKernel(S.fn_sample_costate, (unsigned)pcs::sample_blocks(n_t, 256), 1, 1, 256, 1, 1, 0, s->h->stream, nullptr,
+                               cfg));
+}
+
 int solution_create(pc_handle* h, const double* x, bool x_on_device, int n_orders, const int32_t* orders, const double* tabD,
                     const double* tabU, const double* tau, pc_solution** out) {
   return guarded([&] {
@@ -151,6 +261,12 @@ pc_solution::Phase& solution_phase(pc_solution* s, int phase) {
   if (phase < 0 || phase >= (int)s->ph.size()) throw std::runtime_error("solution: phase out of range");
   HIP_OK(hipSetDevice(s->h->device));
   return *s->ph[phase];
+}
+
+pc_solution::Phase& solution_costate_phase(pc_solution* s, int phase) {
+  auto& S = solution_phase(s, phase);
+  if (!s->has_costate) throw std::runtime_error("solution: no multipliers were set");
+  return S;
 }
 
 void solution_down(double* dst, const DevBuf<double>& src, size_t count) {
@@ -238,6 +354,62 @@ int pc_solution_sample_device(pc_solution* sol, int phase, const double* d_t, in
     pcs::check_sample_args((int)sol->ph.size(), phase, d_t, n_t, flags);
     (void)solution_phase(sol, phase);
     solution_launch_sample(sol, phase, d_t, n_t, flags, d_y, d_dy, d_u, d_f);
+  });
+}
+
+int pc_solution_set_multipliers(pc_solution* sol, const double* lam, int64_t n_lam, int n_orders, const int32_t* orders,
+                                const double* tabA) {
+  return solution_set_multipliers(sol, lam, n_lam, false, n_orders, orders, tabA);
+}
+
+int pc_solution_set_multipliers_device(pc_solution* sol, const double* d_lam, int64_t n_lam, int n_orders, const int32_t* orders,
+                                       const double* tabA) {
+  return solution_set_multipliers(sol, d_lam, n_lam, true, n_orders, orders, tabA);
+}
+
+int pc_solution_costate_nodes(pc_solution* sol, int phase, double* p, double* H, double* nu) {
+  return guarded([&] {
+    auto& S = solution_costate_phase(sol, phase);
+    const size_t N = (size_t)S.plan.N;
+    solution_down(p, S.node_p, N * S.NY);
+    solution_down(H, S.node_H, N);
+    solution_down(nu, S.nu, (size_t)S.NQ);
+  });
+}
+
+int pc_solution_costate_coefficients(pc_solution* sol, int phase, double* p_coef) {
+  return guarded([&] {
+    auto& S = solution_costate_phase(sol, phase);
+    solution_down(p_coef, S.coef_p, (size_t)S.plan.NC * S.NY);
+  });
+}
+
+int pc_solution_sample_costate(pc_solution* sol, int phase, const double* t, int64_t n_t, int flags, double* p, double* H) {
+  return guarded([&] {
+    if (!sol) throw std::runtime_error("null solution");
+    pcs::check_sample_args((int)sol->ph.size(), phase, t, n_t, flags);
+    auto& S = solution_costate_phase(sol, phase);
+    if (n_t == 0) return;
+    const size_t Qn = (size_t)n_t;
+    DevBuf<double> d_t, d_p, d_H;
+    d_t.upload(std::vector<double>(t, t + Qn));
+    d_p.alloc(Qn * (size_t)std::max(1, S.NY));
+    d_H.alloc(Qn);
+    solution_launch_sample_costate(sol, phase, d_t.p, n_t, flags, d_p.p, d_H.p);
+    HIP_OK(hipStreamSynchronize(sol->h->stream));
+    solution_down(p, d_p, Qn * S.NY);
+    solution_down(H, d_H, Qn);
+  });
+}
+
+int pc_solution_sample_costate_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_p,
+                                      double* d_H) {
+  return guarded([&] {
+    if (!sol) throw std::runtime_error("null solution");
+    pcs::check_sample_args((int)sol->ph.size(), phase, d_t, n_t, flags);
+    auto& S = solution_costate_phase(sol, phase);
+    if (n_t > 0 && (!d_H || (S.NY > 0 && !d_p))) throw std::runtime_error("solution: null output");
+    solution_launch_sample_costate(sol, phase, d_t, n_t, flags, d_p, d_H);
   });
 }
 

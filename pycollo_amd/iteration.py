@@ -224,9 +224,13 @@ class MeshIteration:
         """The NLP point ``x_tilde`` as a :class:`pycollo_amd.solution.Solution` (the reference's ``Solution``,
         pycollo/solution/casadi_solution.py:15-86, with dense output sampled on the device).  The node states and
         controls are those of :meth:`solution`; they are unscaled with the scaling the NLP functions were generated
-        with (the engine's), which is this iteration's unless ``update_scaling`` averaged it afterwards."""
+        with (the engine's), which is this iteration's unless ``update_scaling`` averaged it afterwards.  When an
+        interior-point solve has run, its multipliers (``result.lam``) are passed on and the solution carries
+        ``costate`` / ``hamiltonian`` / ``integrand_multiplier``."""
         from .solution import Solution
-        return Solution(self.engine, self.x_tilde, objective=getattr(self, "objective", None))
+        # after an interior-point solve the multipliers of every row come along: costates and the Hamiltonian
+        lam = getattr(getattr(self, "result", None), "lam", None)
+        return Solution(self.engine, self.x_tilde, objective=getattr(self, "objective", None), multipliers=lam)
 
     def solve_with_scipy(self, maxiter: int = 500, tol: float = 1e-9, verbose: int = 0):
         """Solve the scaled NLP with scipy's trust-region interior point method (stand-in for IPOPT)."""

@@ -21,6 +21,29 @@ What the interpolant is, per section k with n nodes, section variable c in [-1, 
 
 It reports the NLP's variables: variables eliminated as constants are not re-inserted (the scope of
 ``MeshIteration.solution()``).
+
+Costates and the Hamiltonian (``multipliers=``; no reference counterpart).  Per phase: N is the number of
+nodes; section k has n_k nodes and its first node is s_k; h_k = tau[s_{k+1}] - tau[s_k]; A^(n) is the (n-1) x n
+integration table.  Defect row r of state a in section k is global row s_k + r of that state's N - 1 rows; its value
+is c~ = W_a (y_{s_k} - y_{s_k+r+1} + stretch h_k sum_j A^(n_k)[r][j] f_a(node s_k + j)).  w is the objective scaling,
+W the per-OCP-row constraint scaling the handle holds.  Then:
+
+* Lam = W lam~ / w for the defect rows (Lam_a) and for the integral rows (Lam_q): the multipliers of the unscaled rows
+  for the unscaled objective.
+* omega_j = sum over the one or two sections containing node j of h_k A^(n_k)[n_k - 2][pos_k(j)].  (The last row of A
+  sums to 1 under both methods and is the Lobatto weights; the Radau weight table sums to 2.)
+* p_a(j) = ( sum_{k contains j} h_k sum_{r=0}^{n_k-2} Lam_a[s_k + r] A^(n_k)[r][pos_k(j)] ) / omega_j where
+  omega_j != 0.  A node with omega_j = 0 is the Radau phase-final node only (the table entry is an exact zero: the
+  node is not collocated); there p_a(N - 1) = Lam_a[N - 2], the multiplier of the phase's last defect row.
+* nu_m = -Lam_q[m]: the weight of integrand m in the Hamiltonian (1 when J = q).
+* H(j) = sum_a p_a(j) f_a(j) + sum_m nu_m g_m(j), f and g the dynamics and integrands at the node's (y, u, q, t, s).
+  No path-constraint term: by complementarity it is zero at a solution.  At the Radau phase-final node, whose control
+  the NLP does not determine, H is NaN.
+* Summation order: lower section first, rows ascending, then the upper section, one division at the end.  A shared
+  node is computed by both of its sections in exactly this order (bit-equal); the section the node opens writes it.
+* Between the nodes p_a on section k is the degree n_k - 1 interpolant through the section's n_k node values, held as
+  Legendre coefficients formed with the ``C_u`` table like u; H(t) is formed from the interpolated p(t) and the model
+  at the interpolated (y(t), u(t)), the route by which ``sample(..., residual=True)`` forms f.
 """
 from __future__ import annotations
 
@@ -132,11 +155,15 @@ def normalise_query(t, tau):
 
 
 class Solution:
-    """``Solution(engine, x_tilde, objective=None)``: the NLP point ``x_tilde`` (scaled; a NumPy array or a torch device
-    tensor, e.g. the resident solver's iterate) of ``engine`` as node values and dense output.  Holds device memory:
-    ``close()`` it (or let it go) before the engine is closed."""
+    """``Solution(engine, x_tilde, objective=None, multipliers=None)``: the NLP point ``x_tilde`` (scaled; a NumPy array
+    or a torch device tensor, e.g. the resident solver's iterate) of ``engine`` as node values and dense output.
+    ``multipliers``: the scaled multipliers of the ``engine.num_c`` constraint rows at that point (NumPy array or torch
+    device tensor, contiguous float64), belonging to the scaling the engine holds now; with them ``costate``
+    ([n_y][N] per phase), ``hamiltonian`` ([N] per phase) and ``integrand_multiplier`` ([n_q] per phase) are filled and
+    :meth:`sample_costate` works; without them the three are ``None``.  Holds device memory: ``close()`` it (or let it
+    go) before the engine is closed."""
 
-    def __init__(self, engine, x_tilde, objective=None):
+    def __init__(self, engine, x_tilde, objective=None, multipliers=None):
         self.engine = engine
         self._lib = engine._lib
         self._h = C.c_void_p()
@@ -203,6 +230,13 @@ class Solution:
         self.initial_time = tuple(t0s)
         self.final_time = tuple(tFs)
         self.parameter = x[lay.s_off:lay.s_off + lay.n_s].copy()
+        self.costate = self.hamiltonian = self.integrand_multiplier = None
+        if multipliers is not None:
+            try:
+                self._set_multipliers(multipliers, orders)
+            except Exception:
+                self.close()
+                raise
 
     # ---- plumbing ----------------------------------------------------------------------------------
     @staticmethod
@@ -220,7 +254,45 @@ class Solution:
         lib.pc_solution_coefficients.argtypes = [vp, C.c_int, vp, vp]
         lib.pc_solution_sample.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
         lib.pc_solution_sample_device.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
+        lib.pc_solution_set_multipliers.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp]
+        lib.pc_solution_set_multipliers_device.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp]
+        lib.pc_solution_costate_nodes.argtypes = [vp, C.c_int, vp, vp, vp]
+        lib.pc_solution_costate_coefficients.argtypes = [vp, C.c_int, vp]
+        lib.pc_solution_sample_costate.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp]
+        lib.pc_solution_sample_costate_device.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp]
         lib._pc_solution_declared = True
+
+    def _set_multipliers(self, lam, orders):
+        """``pc_solution_set_multipliers``: the costate kernel on the multipliers, then the node values."""
+        engine = self.engine
+        od = np.ascontiguousarray(orders, dtype=np.int32)
+        tabA = np.ascontiguousarray(np.concatenate([np.asarray(engine.quad.A(n), dtype=np.float64).ravel() for n in orders]))
+        if _is_torch(lam):
+            import torch
+            if lam.dtype != torch.float64 or lam.dim() != 1 or lam.numel() != engine.num_c or not lam.is_contiguous() \
+                    or not lam.is_cuda:
+                raise ValueError(f"multipliers must be a contiguous float64 device tensor of {engine.num_c} entries")
+            torch.cuda.current_stream(lam.device).synchronize()
+            ok = self._lib.pc_solution_set_multipliers_device(self._h, lam.data_ptr(), lam.numel(), len(od), od.ctypes.data,
+                                                              tabA.ctypes.data)
+        else:
+            lam = np.asarray(lam)
+            if lam.dtype != np.float64 or lam.shape != (engine.num_c,) or not lam.flags.c_contiguous:
+                raise ValueError(f"multipliers must be a contiguous float64 array of {engine.num_c} entries")
+            ok = self._lib.pc_solution_set_multipliers(self._h, lam.ctypes.data, lam.shape[0], len(od), od.ctypes.data,
+                                                       tabA.ctypes.data)
+        self._check(ok)
+        costate, hamiltonian, nu = [], [], []
+        for ip, (pm, pl) in enumerate(zip(engine.model.phases, engine.layout.phases)):
+            p, H, v = np.empty((pm.n_y, pl.N)), np.empty(pl.N), np.empty(pm.n_q)
+            self._check(self._lib.pc_solution_costate_nodes(self._h, ip, p.ctypes.data if p.size else None, H.ctypes.data,
+                                                            v.ctypes.data if v.size else None))
+            costate.append(p)
+            hamiltonian.append(H)
+            nu.append(v)
+        self.costate = tuple(costate)
+        self.hamiltonian = tuple(hamiltonian)
+        self.integrand_multiplier = tuple(nu)
 
     def _check(self, ok):
         if not ok:
@@ -281,6 +353,29 @@ class Solution:
             for b in range(pl.n_u):
                 u_p[b, k] = Legendre(uc[b, sl], domain=dom)
         return y_p, dy_p, u_p
+
+    def quadrature_weights(self, phase: int) -> np.ndarray:
+        """omega [N] of the costate definition: the node weights of the phase's quadrature in tau, from the last rows
+        of the sections' integration tables (they sum to 2, the length of [-1, 1]; the Radau phase-final node has
+        none).  ``sum(omega * hamiltonian) / sum(omega)`` over the weighted nodes is the mean the NLP's stationarity
+        in the final time speaks about."""
+        phase = self._phase(phase, need_handle=False)
+        mesh, quad = self.engine.meshes[phase], self.engine.quad
+        w = np.zeros(mesh.N)
+        for k in range(mesh.K):
+            s, n = int(mesh.s[k]), int(mesh.n[k])
+            w[s:s + n] += (mesh.tau[int(mesh.s[k + 1])] - mesh.tau[s]) * quad.A(n)[n - 2]
+        return w
+
+    def costate_coefficients(self, phase: int):
+        """p_coef [n_y][N + K - 1], laid out like the controls' coefficients (``pc_solution_costate_coefficients``)."""
+        phase = self._phase(phase)
+        if self.costate is None:
+            raise ValueError("the solution was made without multipliers: it has no costates")
+        pl = self.engine.layout.phases[phase]
+        pc = np.empty((pl.n_y, pl.N + pl.K - 1))
+        self._check(self._lib.pc_solution_costate_coefficients(self._h, phase, pc.ctypes.data if pc.size else None))
+        return pc
 
     # ---- dense output ------------------------------------------------------------------------------
     def sample(self, phase: int, t=None, *, tau=None, residual: bool = False, extrapolate: bool = False):
@@ -343,3 +438,50 @@ class Solution:
         ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
         self._check(self._lib.pc_solution_sample(self._h, phase, ptr(q), Q, flags, ptr(y), ptr(dy), ptr(u), ptr(f)))
         return y, dy, u, f
+
+    def sample_costate(self, phase: int, t=None, *, tau=None, extrapolate: bool = False):
+        """``(p [n_y][Q], H [Q])`` at the Q times ``t`` (or abscissae ``tau``) of one phase: the costates' section
+        interpolants and the Hamiltonian formed from them and the model at the interpolated (y(t), u(t)).  Queries, range
+        checks and array types as in :meth:`sample`.  ``ValueError`` if the solution was made without multipliers."""
+        if self.costate is None:
+            raise ValueError("the solution was made without multipliers: it has no costates")
+        q, is_tau = normalise_query(t, tau)
+        phase = self._phase(phase, need_handle=False)
+        t0, tF = self.initial_time[phase], self.final_time[phase]
+        flags = (PC_SOLUTION_TAU if is_tau else 0) | (PC_SOLUTION_EXTRAPOLATE if extrapolate else 0)
+        Q = int(q.shape[0])
+        if _is_torch(q):
+            import torch
+            if q.dtype != torch.float64 or not q.is_cuda:
+                raise ValueError("a tensor of queries must be float64 on the GPU")
+            q = q.contiguous()
+            if Q:
+                has_nan = bool(torch.isnan(q).any())
+                lo, hi, slack = _tau_extremes(float(q.min()), float(q.max()), is_tau, t0, tF)
+                check_queries(lo, hi, has_nan, extrapolate, slack)
+            self._phase(phase)
+            pl = self.engine.layout.phases[phase]
+            p = torch.empty((pl.n_y, Q), dtype=torch.float64, device=q.device)
+            H = torch.empty((Q,), dtype=torch.float64, device=q.device)
+            ptr = lambda a: a.data_ptr() if a.numel() else None   # noqa: E731
+            torch.cuda.current_stream(q.device).synchronize()     # the handle's stream is not torch's
+            self._check(self._lib.pc_solution_sample_costate_device(self._h, phase, ptr(q), Q, flags, ptr(p), ptr(H)))
+            self._check(self._lib.pc_synchronize(self.engine._h))
+        else:
+            q = np.ascontiguousarray(q)
+            if Q:
+                has_nan = bool(np.isnan(q).any())
+                lo, hi, slack = _tau_extremes(0.0 if has_nan else float(q.min()), 0.0 if has_nan else float(q.max()), is_tau, t0, tF)
+                check_queries(lo, hi, has_nan, extrapolate, slack)
+            self._phase(phase)
+            p, H = self.sample_costate_unchecked(phase, q, flags)
+        return p, H
+
+    def sample_costate_unchecked(self, phase, q, flags):
+        """``pc_solution_sample_costate`` as it is: no range check, NaN for a query outside the phase."""
+        pl = self.engine.layout.phases[phase]
+        Q = int(q.shape[0])
+        p, H = np.empty((pl.n_y, Q)), np.empty(Q)
+        ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
+        self._check(self._lib.pc_solution_sample_costate(self._h, phase, ptr(q), Q, flags, ptr(p), ptr(H)))
+        return p, H
