@@ -2106,6 +2106,9 @@ __device__ __forceinline__ void tail_point_apply(const PcTailArgs& A, const Tail
 //   3. f at the ph nodes, Y_ph = y_start + stretch h_k A_(n+1) f_ph          (mesh_refinement.py:199-210)
 //   4. |Y_ph - y_ph| relative to 1 + (1 + max|y_ph|) per state, section maximum (mesh_refinement.py:211-233)
 // ---------------------------------------------------------------------------------------------
+// maximum that keeps a NaN from either side, as np.max does (fmax returns the other operand)
+__device__ __forceinline__ double nan_max(double m, double x) { return (x > m || x != x) ? x : m; }
+
 template <class M>
 __device__ __forceinline__ void mesh_error(const PcRefineArgs& A) {
   using St = S<M>;
@@ -2216,8 +2219,8 @@ __device__ __forceinline__ void mesh_error(const PcRefineArgs& A) {
       const double Yph = s_yp[a * TB + l0] + stretch * (h * acc);
       const double err = fabs(Yph - s_yp[a * TB + tid]);
       double mx = 0.0;
-      for (int i = 1; i <= n; ++i) mx = fmax(mx, fabs(s_yp[a * TB + l0 + i]));
-      rel = fmax(rel, err / (1.0 + (mx + 1.0)));
+      for (int i = 1; i <= n; ++i) mx = nan_max(mx, fabs(s_yp[a * TB + l0 + i]));
+      rel = nan_max(rel, err / (1.0 + (mx + 1.0)));
       s_ae[a * TB + tid] = err;
     });
     s_re[tid] = rel;
@@ -2225,12 +2228,12 @@ __device__ __forceinline__ void mesh_error(const PcRefineArgs& A) {
   __syncthreads();
   if (active && j == 0) {
     double m = 0.0;
-    for (int i = 1; i <= n; ++i) m = fmax(m, s_re[l0 + i]);
+    for (int i = 1; i <= n; ++i) m = nan_max(m, s_re[l0 + i]);
     A.max_rel[k] = m;
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
       double ma = 0.0;
-      for (int i = 1; i <= n; ++i) ma = fmax(ma, s_ae[a * TB + l0 + i]);
+      for (int i = 1; i <= n; ++i) ma = nan_max(ma, s_ae[a * TB + l0 + i]);
       A.max_abs[(int64_t)k * NY + a] = ma;
     });
   }

@@ -41,9 +41,11 @@ def brachistochrone(K: int = 10, order: int = 4) -> ProblemSpec:
     return prob
 
 
-def hypersensitive(K: int = 10, order: int = 4, *, test_fixture_bounds: bool = False) -> ProblemSpec:
+def hypersensitive(K: int = 10, order: int = 4, *, test_fixture_bounds: bool = False,
+                   fixed_control: float | None = None) -> ProblemSpec:
     """Betts ex. 4.4; examples/hypersensitive_problem/hypersensitive_problem.py:14-35.
-    ``test_fixture_bounds`` switches to the bounds of tests/unit/conftest.py:193-230."""
+    ``test_fixture_bounds`` switches to the bounds of tests/unit/conftest.py:193-230; ``fixed_control`` gives the
+    control equal bounds, so it is eliminated and the phase has one state and no control (n_u = 0)."""
     y, u = sym.symbols("y u")
     prob = ProblemSpec("Hypersensitive problem")
     ph = prob.new_phase("A")
@@ -62,6 +64,8 @@ def hypersensitive(K: int = 10, order: int = 4, *, test_fixture_bounds: bool = F
         ph.bounds.state_variables = [[-50, 50]]
         ph.bounds.control_variables = [[-50, 50]]
         ph.bounds.integral_variables = [[0, 100000]]
+    if fixed_control is not None:
+        ph.bounds.control_variables = [[float(fixed_control), float(fixed_control)]]
     ph.bounds.initial_state_constraints = [[1.0, 1.0]]
     ph.bounds.final_state_constraints = [[1.5, 1.5]]
     ph.guess.time = np.array([0.0, 10000.0])

@@ -17,6 +17,7 @@ from .quadrature import QuadratureTables
 MESH_TOLERANCE = 1e-7           # pycollo/settings.py default (mesh_refinement.py:329)
 COLLOCATION_POINTS_MIN = 4      # pycollo/quadrature.py:36-37
 COLLOCATION_POINTS_MAX = 10
+MESH_ERROR_ORDER_MIN, MESH_ERROR_ORDER_MAX = 2, 19   # section orders pc_mesh_error has tables for (n + 1 <= 20)
 
 
 def ph_tables(quad: QuadratureTables, n: int):
@@ -24,7 +25,17 @@ def ph_tables(quad: QuadratureTables, n: int):
     evaluated at the n-1 interior nodes of the order-(n+1) rule, and the order-(n+1) integration matrix.
 
     B and E are what ``Legendre.fit(...).integ(k=y0)`` and ``Polynomial.fit(...)`` of
-    solution_abc.py:70-100 evaluate to at the ph nodes (a degree n-1 fit through n points interpolates)."""
+    solution_abc.py:70-100 evaluate to at the ph nodes (a degree n-1 fit through n points interpolates).
+
+    Lobatto only: with Radau points the last "point" of a section is a placeholder and the reference fits through the
+    n - 1 true nodes (solution_abc.py:104); that branch is not restated."""
+    if quad.method != "lobatto":
+        raise NotImplementedError(f"the ph mesh-error tables restate the Lobatto branch only, not quadrature method "
+                                  f"'{quad.method}'")
+    n = int(n)
+    if not MESH_ERROR_ORDER_MIN <= n <= MESH_ERROR_ORDER_MAX:
+        raise ValueError(f"mesh-error tables: section order {n} outside [{MESH_ERROR_ORDER_MIN}, {MESH_ERROR_ORDER_MAX}] "
+                         f"(the estimate needs the quadrature tables of order n + 1 <= {MESH_ERROR_ORDER_MAX + 1})")
     x = quad.points(n)                      # solution nodes on [-1, 1]
     xp = quad.points(n + 1)[1:-1]           # interior ph nodes
     V = _leg.legvander(x, n - 1)            # V[i, k] = P_k(x_i)
@@ -42,6 +53,15 @@ def ph_tables(quad: QuadratureTables, n: int):
 
 def mesh_error(engine, x_tilde):
     """Per phase: (max relative error per section [K], max absolute error per section and state [K][n_y])."""
+    if engine.quad.method != "lobatto":
+        raise NotImplementedError(f"mesh_error restates the Lobatto branch of the reference's section fits only, not "
+                                  f"quadrature method '{engine.quad.method}'")
+    for ip, mesh in enumerate(engine.meshes):
+        lo, hi = int(np.min(mesh.n)), int(np.max(mesh.n))
+        if lo < MESH_ERROR_ORDER_MIN or hi > MESH_ERROR_ORDER_MAX:
+            raise ValueError(f"mesh_error: phase {ip} has sections of order {lo if lo < MESH_ERROR_ORDER_MIN else hi}, outside "
+                             f"[{MESH_ERROR_ORDER_MIN}, {MESH_ERROR_ORDER_MAX}] (the estimate needs the quadrature tables "
+                             f"of order n + 1 <= {MESH_ERROR_ORDER_MAX + 1})")
     out = []
     for ip, mesh in enumerate(engine.meshes):
         orders = sorted({int(n) for n in np.unique(mesh.n)})
@@ -113,6 +133,11 @@ def next_phase_mesh(sizes, nodes, max_rel_err, *, mesh_tol=MESH_TOLERANCE, n_min
     sizes = np.asarray(sizes, dtype=float)
     nodes = np.asarray(nodes, dtype=np.int64)
     err = np.asarray(max_rel_err, dtype=float)
+    if not np.all(np.isfinite(err)):
+        # a NaN compares false with everything: "not max > tol" would read it as "tolerance met"
+        bad = np.flatnonzero(~np.isfinite(err))
+        raise ValueError(f"next_phase_mesh: the mesh error of section {int(bad[0])} is not finite ({err[bad[0]]}); "
+                         f"{bad.size} of {err.size} sections are not")
     if not np.max(err) > mesh_tol:
         return sizes / sizes.sum(), nodes.copy(), True
     with np.errstate(divide="ignore", invalid="ignore"):

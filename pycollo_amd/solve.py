@@ -81,7 +81,7 @@ def solve_ocp(problem, *, max_mesh_iterations: int = 10, mesh_tolerance: float =
         res = it.solve_with_ipm(max_iter=nlp_max_iter, tol=nlp_tol, verbose=max(0, verbose - 1), linear_solver=linear_solver,
                                 warm_start=warm_start, host_retry=host_retry)
         errs = mesh_error(it.engine, it.x_tilde)
-        worst = max(float(np.max(rel)) for rel, _ in errs)
+        worst = float(np.max([np.max(rel) for rel, _ in errs]))   # (np.max: a NaN of any phase stays)
         log.append({"K": [int(m.K) for m in it.meshes], "N": [int(pl.N) for pl in it.layout.phases],
                     "objective": float(it.objective), "status": res.status, "nlp_iterations": int(res.iterations),
                     "max_rel_err": worst, "seconds": float(res.seconds), "evaluations": dict(res.evaluations)})
@@ -99,6 +99,12 @@ def solve_ocp(problem, *, max_mesh_iterations: int = 10, mesh_tolerance: float =
             print(f"mesh iteration {k + 1}: K={log[-1]['K']} N={log[-1]['N']} J={it.objective:.10g} "
                   f"[{res.status}, {res.iterations} NLP iterations, {res.seconds:.2f} s] max rel. mesh error {worst:.3e}", flush=True)
         if not res.success:
+            break
+        if not np.isfinite(worst):
+            # f is not finite somewhere on the solution or on the ph mesh: no estimate, so the tolerance is NOT met
+            import warnings
+            warnings.warn(f"mesh iteration {k + 1}: the mesh-error estimate is not finite ({worst}); the mesh tolerance is "
+                          f"not met and the mesh is not refined further", RuntimeWarning, stacklevel=2)
             break
         done_all = True
         new_meshes = []

@@ -111,11 +111,15 @@ def _indptr(eng):
     return np.concatenate([[0], np.cumsum(np.bincount(r, minlength=eng.num_c))])
 
 
-@pytest.mark.parametrize("then", ["hessian", "row_norms"])
+@pytest.mark.parametrize("then", ["hessian", "row_norms", "mesh_error"])
 def test_prefetch_off_jacobian_after_other_calls(built, then):
     """pc_set_prefetch_jac(0), kernels not writing host memory: G~ stays on the device until pc_eval_jac_g asks for
     it.  A pc_eval_h (or a row-norm pass) in between drains the stream; the Jacobian requested afterwards at the same
-    point (new_x = 0) must still be fetched -- not the pinned block's previous contents."""
+    point (new_x = 0) must still be fetched -- not the pinned block's previous contents.
+
+    ``mesh_error``: pc_mesh_error stages ANOTHER point through the handle's device copy of x and clears the cache
+    flags; the callbacks that follow at the first point with new_x = 0 -- as a caller does who knows nothing of the
+    estimate in between -- must return the bits of the first evaluation, not values of the estimate's point."""
     prob = problems.cart_pole(K=40, order=4)
     eng = _engine(prob)
     ora = OracleNlp(prob, golden_tables("lobatto"), V_ocp=eng.V_ocp, r_ocp=eng.r_ocp, W_ocp=eng.W_ocp, w_J=1.0)
@@ -123,6 +127,27 @@ def test_prefetch_off_jacobian_after_other_calls(built, then):
     x0, x1 = rng.uniform(-0.4, 0.4, eng.num_x), rng.uniform(-0.4, 0.4, eng.num_x)
     lam = rng.normal(size=eng.num_c)
     eng.set_host_mode(0)
+    if then == "mesh_error":
+        from pycollo_amd.refinement import mesh_error
+        for prefetch in (True, False):
+            eng.set_prefetch_jac(prefetch)
+            first = (eng.evaluate_c(x0), eng.evaluate_G_nonzeros(x0, new_x=False),
+                     eng.evaluate_H_nonzeros(x0, 0.9, lam, new_x=False))
+            assert_matches_oracle(ora, x0, c=first[0], G=first[1], H=first[2], sigma=0.9, lam=lam)
+            (rel, _), = mesh_error(eng, x1)
+            assert rel.shape == (40,) and np.all(rel > 0)
+            again = (eng.evaluate_c(x0, new_x=False), eng.evaluate_G_nonzeros(x0, new_x=False),
+                     eng.evaluate_H_nonzeros(x0, 0.9, lam, new_x=False))
+            for a, b in zip(first, again):
+                np.testing.assert_array_equal(a, b)
+            all_first = eng.evaluate_all(x0, 0.9, lam)
+            mesh_error(eng, x1)
+            for a, b in zip(all_first, eng.evaluate_all(x0, 0.9, lam)):
+                np.testing.assert_array_equal(a, b)
+            for a, b in zip(first, all_first):
+                np.testing.assert_array_equal(a, b)
+        eng.close()
+        return
     eng.set_prefetch_jac(True)
     eng.evaluate_G_nonzeros(x0)            # the pinned block now holds G~(x0)
     eng.set_prefetch_jac(False)
@@ -188,4 +213,49 @@ def test_cyipopt_object_survives_device_api_calls(built):
     step(1.0)
     s.synchronize()
     assert abs(eng.evaluate_J(x, new_x=False) - ora.J(x)) <= TOL * max(1.0, abs(ora.J(x)))
+    eng.close()
+
+
+def test_device_api_is_unaffected_by_a_mesh_error_in_between(built):
+    """The device-resident entry points read the caller's x, not the handle's mirror that pc_mesh_error overwrites:
+    evaluate_all_device / a bound step at x1, the estimate at x2, the same launch again -- the same bits in c~, G~, H~."""
+    import torch
+    from pycollo_amd.refinement import mesh_error
+    prob = problems.cart_pole(K=40, order=4)
+    eng = _engine(prob)
+    ora = OracleNlp(prob, golden_tables("lobatto"), V_ocp=eng.V_ocp, r_ocp=eng.r_ocp, W_ocp=eng.W_ocp, w_J=1.0)
+    rng = np.random.default_rng(31)
+    x1, x2 = rng.uniform(-0.4, 0.4, eng.num_x), rng.uniform(-0.4, 0.4, eng.num_x)
+    lam = rng.normal(size=eng.num_c)
+    dev = torch.device("cuda", 0)
+    dx, dl = torch.from_numpy(x1).to(dev), torch.from_numpy(lam).to(dev)
+    dc = torch.empty(eng.num_c, dtype=torch.float64, device=dev)
+    dG = torch.empty(eng.nnz_jac, dtype=torch.float64, device=dev)
+    dH = torch.empty(eng.nnz_hess, dtype=torch.float64, device=dev)
+    s = torch.cuda.Stream(device=dev)
+
+    def read():
+        s.synchronize()
+        out = tuple(t.cpu().numpy().copy() for t in (dc, dG, dH))
+        for t in (dc, dG, dH):
+            t.fill_(float("nan"))
+        torch.cuda.synchronize(dev)
+        return out
+    eng.evaluate_all_device(dx, 0.9, dl, dc, dG, dH, s.cuda_stream)
+    first = read()
+    assert_matches_oracle(ora, x1, c=first[0], G=first[1], H=first[2], sigma=0.9, lam=lam)
+    mesh_error(eng, x2)
+    eng.evaluate_all_device(dx, 0.9, dl, dc, dG, dH, s.cuda_stream)
+    for a, b in zip(first, read()):
+        np.testing.assert_array_equal(a, b)
+    step = eng.bind_device(dx, dl, dc, dG, dH, s.cuda_stream)
+    step(0.9)
+    for a, b in zip(first, read()):
+        np.testing.assert_array_equal(a, b)
+    mesh_error(eng, x2)
+    step(0.9)
+    for a, b in zip(first, read()):
+        np.testing.assert_array_equal(a, b)
+    # ... and the host callbacks after it still describe their own point
+    assert_matches_oracle(ora, x1, c=eng.evaluate_c(x1), G=eng.evaluate_G_nonzeros(x1, new_x=False))
     eng.close()
