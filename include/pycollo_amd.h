@@ -123,7 +123,12 @@ typedef struct {
   int64_t algorithmic_bytes;       /* 8*(n+m) read + 8*(m+nnz_jac+nnz_hess) written per eval_all */
   int32_t n_tiles_total, threads_per_block;   /* threads_per_block = nodes per tile (plus the shared end node) */
   int32_t lds_bytes_max, n_launches; /* kernels per eval_all */
-  int32_t waves_per_tile, reserved;  /* largest replica count of a phase (1, 2 or 4): workgroup = tile x this */
+  int32_t waves_per_tile;          /* largest replica count of a phase (1, 2 or 4): workgroup = tile x this */
+  int32_t last_launch;             /* which builds the handle's last evaluation launched (0: none yet) -- bit 0: resident
+                                      (the tail inside the one launch); bit 1: pc_tail_big was the separate tail; bit 2:
+                                      one launch covered every phase of a multi-phase problem; bits 4-6: workgroups of the
+                                      resident tail (0 when the tail was a launch of its own or did not run); bits 8-11:
+                                      threads / 64 of the workgroup that ran the tail */
 } pc_info;
 
 const char* pc_last_error(void);
@@ -333,6 +338,22 @@ int pc_kkt_plan_entries(const pc_kkt_plan* plan, int64_t n, int64_t nv, int64_t 
 const char* pc_kkt_last_error(void);
 int pc_kkt_create(const pc_kkt_desc* desc, const double* d_jac, const double* d_hess, int device, pc_kkt** out);
 void pc_kkt_destroy(pc_kkt* k);
+/* Which of the solver's builds the handle runs (chosen in pc_kkt_create from the block counts and the PYCOLLO_AMD_KKT_*
+ * environment, all read there). */
+typedef struct {
+  int64_t n_leaf, n_chain, nb;
+  int64_t n_mv_long;               /* rows of the product cut into chunks */
+  int32_t chain_cr;                /* 1: the chain by cyclic reduction, one launch per level; 0: node by node */
+  int32_t cr_levels;               /* levels of the cyclic reduction (0 without it) */
+  int32_t cr_top_levels;           /* trailing levels the substitutions run in one launch (kkt_cr_top); 0: none */
+  int32_t cr_top_waves;            /* waves of that launch's workgroup */
+  int32_t border_blocks;           /* workgroups that sum the border terms (kkt_border_terms); 0: the border kernel's own walk */
+  int32_t leaf_forward_stage;      /* kkt_leaf_forward of the last solve -- 0: from device memory, 1 / 2: the leaf staged in
+                                      LDS by one / two waves; -1: no solve yet (or no leaves) */
+  int32_t leaf_waves;              /* waves per leaf of kkt_leaf_factor */
+  int32_t reserved;
+} pc_kkt_info;
+int pc_kkt_get_info(const pc_kkt* k, pc_kkt_info* info);
 /* assemble from the current device G~ / H~ (use_hess = 0: W = 0, e.g. least-squares multipliers) and dvec[nu]
  * (host: Sigma + dw on primal unknowns, -dc on multipliers), factorise; returns the pivot signs */
 int pc_kkt_factor(pc_kkt* k, int use_hess, const double* dvec, int32_t* n_pos, int32_t* n_neg);

@@ -214,6 +214,7 @@ struct pc_handle {
   PinBuf<double> h_norms;
   std::vector<double> V_ocp, r_ocp, W_ocp;
   int n_launches = 0;
+  int last_launch = 0;                       // pc_info.last_launch: the builds the last evaluation launched
   int lds_max = 0;
   int lds_limit = 64 * 1024;  // dynamic LDS a workgroup may request (queried from the device)
   // derivative check (pc_deriv.hpp, pc_deriv_check.hpp): colouring plan and scratch, built on first use
@@ -380,6 +381,7 @@ void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_
     t.epoch = h->epoch;
   };
   if (res && ++h->epoch == 0) h->epoch = 1;   // (zero is the tag of never-written granules)
+  int last = 0;   // -> h->last_launch
   struct MultiRes {
     PcMultiArgs m;
     PcTailArgs t;
@@ -424,6 +426,7 @@ void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_
       void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &mr, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
       HIP_OK(hipModuleLaunchKernel(h->bulk_all_res_fn, nb + ntb, 1, 1, bt, 1, 1,
                                    std::max(h->lds_all, h->tail_lds_bytes), st, nullptr, cfg));
+      h->last_launch = 1 | 4 | (ntb << 4) | ((bt / 64) << 8);
       return;
     }
     if (nb > 0) {
@@ -431,6 +434,7 @@ void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_
       void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &m, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
       HIP_OK(hipModuleLaunchKernel(h->bulk_all_fn, nb, 1, 1, h->TB * h->wpt_all, 1, 1, h->lds_all, st, nullptr, cfg));
     }
+    last |= 4;
     bulk = false;
   }
   struct BulkRes {   // what the host hands to pc_bulk_p<i>_r: (lead scalars..., PcPhaseArgs a, PcTailArgs t)
@@ -465,12 +469,14 @@ void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_
       void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &br, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
       HIP_OK(hipModuleLaunchKernel(D.fn_res, D.n_tiles + ntb, 1, 1, a.block_threads, 1, 1,
                                    std::max(D.lds_bytes, h->tail_lds_bytes), st, nullptr, cfg));
+      h->last_launch = 1 | (ntb << 4) | ((a.block_threads / 64) << 8);
       return;
     }
     size_t sz = sizeof(ba);
     void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ba, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
     HIP_OK(hipModuleLaunchKernel(D.fn, D.tile_end - D.tile_begin, 1, 1, h->TB * D.wpt, 1, 1, D.lds_bytes, st, nullptr, cfg));
   }
+  h->last_launch = last;
   if (!tail) return;
   PcTailLaunch& tl = h->host_tail_launch;
   PcTailArgs& t = tl.t;
@@ -483,6 +489,7 @@ void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_
   for (size_t ip = 0; ip < Q.ph.size(); ++ip) max_tiles = std::max(max_tiles, (int)t.ph[ip].n_tiles);
   hipFunction_t fn = (h->tail_big_fn && max_tiles > 4 * PC_TAIL_THREADS) ? h->tail_big_fn : h->tail_fn;
   HIP_OK(hipModuleLaunchKernel(fn, 1, 1, 1, PC_TAIL_THREADS, 1, 1, h->tail_lds_bytes, st, nullptr, cfg));
+  h->last_launch = last | (fn == h->tail_big_fn ? 2 : 0) | ((PC_TAIL_THREADS / 64) << 8);
 }
 
 void upload_scaling(pc_handle* h) {
@@ -1186,7 +1193,7 @@ int pc_get_info(const pc_handle* h, pc_info* info) {
     info->waves_per_tile = 1;
     for (auto& D : h->pd) info->waves_per_tile = std::max(info->waves_per_tile, (int32_t)D->wpt);
     if (h->bulk_all_fn) info->waves_per_tile = h->wpt_all;
-    info->reserved = 0;
+    info->last_launch = h->last_launch;
   });
 }
 

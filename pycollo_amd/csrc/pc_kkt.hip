@@ -986,6 +986,9 @@ struct pc_kkt {
   // unchanged in all ten printed digits, 1e-11 1.06 ms (objective moves in the 8th digit), 1e-9 0.95 ms
   // (profiles/r04_ipm_iter_time.txt)
   double resid_tol = 1e-12;
+  int leaf_fwd_env = -1;     // PYCOLLO_AMD_KKT_LEAF_FWD_LDS: kkt_leaf_forward's staging (0 / 1 / 2); -1: by the leaf count
+  int leaf_waves = 4;        // PYCOLLO_AMD_KKT_LEAF_WAVES: waves per leaf of kkt_leaf_factor
+  int leaf_forward_stage = -1;   // what the last forward elimination ran (pc_kkt_info)
 };
 
 // Wait for the stream by polling first: a blocking wait costs an interrupt and a wake-up (10-20 us on the MI355X host),
@@ -1049,8 +1052,8 @@ static void forward_device(pc_kkt* k, const double* d_rhs) {
   if (k->n_leaf) {
     // (two waves and the leaf in LDS: pc_kkt_solve 0.199 -> 0.183 ms at config 2, 0.425 -> 0.410 at config 3; with the shuttle's
     //  6 000 leaves the LDS costs occupancy and the solve got slower, 0.63 -> 0.65-0.71: staged up to 4 096 leaves)
-    static const int stage_env = std::getenv("PYCOLLO_AMD_KKT_LEAF_FWD_LDS") ? std::atoi(std::getenv("PYCOLLO_AMD_KKT_LEAF_FWD_LDS")) : -1;
-    const int stage = stage_env >= 0 ? stage_env : (k->n_leaf <= 4096 ? 2 : 0);
+    const int stage = k->leaf_fwd_env >= 0 ? k->leaf_fwd_env : (k->n_leaf <= 4096 ? 2 : 0);
+    k->leaf_forward_stage = stage;
     KArgs la = k->args;
     la.lds_doubles = stage ? k->lds_leaf_full / 8 : 0;     // (0: solve from device memory, the A/B switch)
     hipLaunchKernelGGL(kkt_leaf_forward, dim3(k->n_leaf), dim3(stage > 1 ? 64 * stage : 64), stage ? k->lds_leaf_full : k->lds_leaf, st, la);
@@ -1164,6 +1167,8 @@ int pc_kkt_create(const pc_kkt_desc* d, const double* d_jac, const double* d_hes
     k->w_norm.alloc(4);
     k->h_norm.alloc(4);
     if (const char* env = std::getenv("PYCOLLO_AMD_KKT_RESID_TOL")) k->resid_tol = std::atof(env);
+    if (const char* env = std::getenv("PYCOLLO_AMD_KKT_LEAF_FWD_LDS")) k->leaf_fwd_env = std::atoi(env);
+    if (const char* env = std::getenv("PYCOLLO_AMD_KKT_LEAF_WAVES")) k->leaf_waves = std::max(1, std::min(16, std::atoi(env)));
     // derived tables
     std::vector<uint8_t> last(d->n_chain, 0);
     for (int64_t p = 0; p < d->n_phase; ++p) last[d->chain_phase_ptr[p + 1] - 1] = 1;
@@ -1486,6 +1491,24 @@ int pc_kkt_plan_entries(const pc_kkt_plan* P, int64_t n, int64_t nv, int64_t nH,
   });
 }
 
+int pc_kkt_get_info(const pc_kkt* k, pc_kkt_info* info) {
+  return guarded([&] {
+    if (!k || !info) throw std::runtime_error("null argument");
+    std::memset(info, 0, sizeof(*info));
+    info->n_leaf = k->n_leaf;
+    info->n_chain = k->n_chain;
+    info->nb = k->nb;
+    info->n_mv_long = k->n_mv_long;
+    info->chain_cr = k->chain_cr ? 1 : 0;
+    info->cr_levels = k->chain_cr ? (int32_t)k->cr_lvl_ptr.size() - 1 : 0;
+    info->cr_top_levels = k->chain_cr ? k->cr_top.n : 0;
+    info->cr_top_waves = k->chain_cr ? k->cr_top_waves : 0;
+    info->border_blocks = k->border_blocks;
+    info->leaf_forward_stage = k->leaf_forward_stage;
+    info->leaf_waves = k->leaf_waves;
+  });
+}
+
 void pc_kkt_destroy(pc_kkt* k) {
   if (!k) return;
   (void)hipSetDevice(k->device);
@@ -1516,8 +1539,7 @@ static void factor_device(pc_kkt* k, int use_hess, const double* d_dvec, int32_t
       // four waves per leaf: 0.246 -> 0.221 ms per factorisation at config 2, 0.644 -> 0.594 at config 3 against two (the
       // trailing update of a pivot step is the parallel part); one wave with LDS-only ordering 0.30 / 0.75, six or eight waves
       // no better than four and 4 % worse on the shuttle's blocks (profiles/r04_ipm_iter_time.txt)
-      static const int leaf_waves = std::getenv("PYCOLLO_AMD_KKT_LEAF_WAVES") ? std::max(1, std::min(16, std::atoi(std::getenv("PYCOLLO_AMD_KKT_LEAF_WAVES")))) : 4;
-      hipLaunchKernelGGL(kkt_leaf_factor, dim3(k->n_leaf), dim3(64 * leaf_waves), k->lds_leaf_full, st, la);
+      hipLaunchKernelGGL(kkt_leaf_factor, dim3(k->n_leaf), dim3(64 * k->leaf_waves), k->lds_leaf_full, st, la);
     }
     if (k->chain_cr) cr_levels_device<0>(k);
     else if (k->n_phase) hipLaunchKernelGGL(kkt_chain_factor, dim3(k->n_phase), dim3(64), k->lds_chain_factor, st, k->args);

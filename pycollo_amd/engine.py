@@ -66,7 +66,7 @@ class _Info(C.Structure):
     _fields_ = [("n", C.c_int32), ("m", C.c_int32), ("nnz_jac", C.c_int64), ("nnz_hess", C.c_int64),
                 ("algorithmic_bytes", C.c_int64), ("n_tiles_total", C.c_int32), ("threads_per_block", C.c_int32),
                 ("lds_bytes_max", C.c_int32), ("n_launches", C.c_int32), ("waves_per_tile", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("last_launch", C.c_int32)]
 
 
 class _DerivEntry(C.Structure):
@@ -339,7 +339,6 @@ class NlpEngine:
             raise RuntimeError("pc_create failed: " + self._lib.pc_last_error().decode())
         info = _Info()
         self._check(self._lib.pc_get_info(self._h, C.byref(info)))
-        self.info = {k: getattr(info, k) for k, _ in _Info._fields_}
         if plan_only:
             return
         self.num_x, self.num_c = info.n, info.m
@@ -423,8 +422,25 @@ class NlpEngine:
         if not ok:
             raise RuntimeError(self._lib.pc_last_error().decode())
 
+    @property
+    def info(self) -> dict:
+        """``pc_info`` as a dict, read from the handle at every access: the sizes and the launch shape, and which builds
+        the last evaluation launched -- ``last_launch`` with its fields decoded: ``resident`` (one launch, the tail inside
+        it), ``tail_big`` (pc_tail_big was the separate tail), ``merged`` (one launch for every phase), ``tail_blocks``
+        (workgroups of the resident tail), ``tail_block_threads`` (threads of the workgroup that ran the tail)."""
+        if not self._h:   # closed: what the handle said last
+            return dict(self._info_closed)
+        info = _Info()
+        self._check(self._lib.pc_get_info(self._h, C.byref(info)))
+        out = {k: getattr(info, k) for k, _ in _Info._fields_}
+        ll = out["last_launch"]
+        out.update(resident=bool(ll & 1), tail_big=bool(ll & 2), merged=bool(ll & 4), tail_blocks=(ll >> 4) & 7,
+                   tail_block_threads=64 * ((ll >> 8) & 15))
+        return out
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
+            self._info_closed = self.info
             self._lib.pc_destroy(self._h)
             self._h = C.c_void_p()
 

@@ -563,6 +563,13 @@ class _Desc(C.Structure):
                 + [(k, C.POINTER(_CTYPE[np.dtype(t)])) for k, t in ARRAY_FIELDS] + [("chain_export", C.POINTER(C.c_uint8))])
 
 
+class _KktInfo(C.Structure):
+    _fields_ = [("n_leaf", C.c_int64), ("n_chain", C.c_int64), ("nb", C.c_int64), ("n_mv_long", C.c_int64),
+                ("chain_cr", C.c_int32), ("cr_levels", C.c_int32), ("cr_top_levels", C.c_int32), ("cr_top_waves", C.c_int32),
+                ("border_blocks", C.c_int32), ("leaf_forward_stage", C.c_int32), ("leaf_waves", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class GpuKkt:
     """The factorisation object: ``pc_kkt_*`` bound to one engine's device-resident G~ / H~."""
 
@@ -583,6 +590,7 @@ class GpuKkt:
         lib.pc_kkt_create.argtypes = [C.POINTER(_Desc), vp, vp, C.c_int, C.POINTER(vp)]
         lib.pc_kkt_destroy.argtypes = [vp]
         lib.pc_kkt_destroy.restype = None
+        lib.pc_kkt_get_info.argtypes = [vp, C.POINTER(_KktInfo)]
         lib.pc_kkt_factor.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         lib.pc_kkt_solve.argtypes = [vp, vp, vp]
         lib.pc_kkt_matvec.argtypes = [vp, C.c_int, vp, vp, vp]
@@ -625,6 +633,15 @@ class GpuKkt:
     def _check(self, ok):
         if not ok:
             raise RuntimeError(self._lib.pc_kkt_last_error().decode())
+
+    @property
+    def info(self) -> dict:
+        """Which builds of the solver the handle runs (``pc_kkt_info``): block counts, the chain's cyclic reduction and
+        the levels its substitutions run in one launch, the grid that sums the border terms, the staging of the last
+        leaf forward elimination (-1 before the first solve), the waves per leaf of the factorisation."""
+        info = _KktInfo()
+        self._check(self._lib.pc_kkt_get_info(self._h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in _KktInfo._fields_ if k != "reserved"}
 
     def factor(self, dvec, use_hess=True):
         """Assemble from the engine's current device G~ / H~ and factorise; returns (n_pos, n_neg) pivots."""
