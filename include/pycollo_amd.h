@@ -577,6 +577,29 @@ int pc_solution_sample_costate(pc_solution* sol, int phase, const double* t, int
 int pc_solution_sample_costate_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_p,
                                       double* d_H);
 
+/* ---- forward propagation under the solution's controls (no reference counterpart) ----
+ * seg_nodes [n_seg + 1]: strictly ascending node indices, first 0, last N - 1.  Segment i is one initial-value problem:
+ * it starts from the NLP's state at node seg_nodes[i] and integrates dy/dc = stretch (w_k / 2) f(y, u(c), q, t0, tF, s)
+ * across the node intervals up to node seg_nodes[i + 1], c the section variable and u(c) the section's control
+ * interpolant (what pc_solution_sample returns), by the Dormand-Prince 5(4) pair; no step straddles a node.
+ *   substeps = m >= 1: m equal steps per node interval, no error control (rtol is not read).
+ *   substeps = 0: adaptive.  Every interval starts with h = the interval; err = max_a |e_a| / (atol_a + rtol max(|y_a|,
+ *     |y_a,new|)); accepted when err <= 1; factor = clamp(0.9 err^(-1/5), 0.2, 5), at most 1 right after a rejection;
+ *     next h = min(h factor, rest of the interval).  max_steps (1 .. 2^20) bounds accepted + rejected per interval.
+ * atol [n_y]: finite and positive (always checked).  Outputs: y_arrive [n_y][N] (column j >= 1: the state arriving at
+ * node j, column 0: y(0)), accepted / rejected [N] (steps of the interval that ends at the node; column 0: 0),
+ * seg_status [n_seg] (-1: complete; else the first node of the interval that used up max_steps: arrivals from there to
+ * the segment's end are NaN, their counts 0 behind the failing interval).  Runs pc_sol_propagate_p<i> on the handle's
+ * stream.  Host pointers for the outputs; synchronises. */
+int pc_solution_propagate(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
+                          const double* atol, int64_t max_steps, double* y_arrive, int32_t* accepted, int32_t* rejected,
+                          int32_t* seg_status);
+/* the same with device pointers for the four outputs (seg_nodes and atol stay host arrays: they are checked and staged
+ * before the launch); queued on the handle's stream, does not synchronise behind the launch */
+int pc_solution_propagate_device(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
+                                 const double* atol, int64_t max_steps, double* d_y_arrive, int32_t* d_accepted,
+                                 int32_t* d_rejected, int32_t* d_seg_status);
+
 /* timing of the last n pc_eval_all_device launches is measured by the caller with HIP events on the
  * stream it passed; this returns the stream the handle owns (hipStream_t) */
 void* pc_stream(pc_handle* h);

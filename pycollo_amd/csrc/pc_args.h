@@ -368,4 +368,29 @@ struct PcSolCostateSampleArgs {
   double* out_H;            // [Q]
 };
 
+// Arguments of the forward propagation (pc_solution.hpp, "propagation"): the dynamics integrated under the
+// solution's control interpolant by Dormand-Prince 5(4), one lane per segment of consecutive node intervals.
+#define PC_SOL_PROP_TB 64              // lanes of a workgroup of pc_sol_propagate
+#define PC_SOL_PROP_MAX_STEPS 1048576  // largest max_steps and largest substeps (2^20): every loop of the kernel is bounded
+struct PcSolPropagateArgs {
+  const double* x;          // [num_x] scaled NLP point (free times; the q / t / s arguments of f)
+  const double* tau;        // [N] node abscissae
+  const int32_t* sec_s;     // [K+1]
+  const double* sec_tau;    // [K+1] tau at the section boundaries
+  const double* node_y;     // [NY][N] the NLP's states: where every segment starts
+  const double* coef_u;     // [NU][NC]
+  const int32_t* seg_node;  // [n_seg+1] segment i integrates the node intervals seg_node[i] .. seg_node[i+1]
+  const int32_t* seg_sec;   // [n_seg] the section of every segment's first interval
+  const double* atol;       // [NY]
+  double* y_arrive;         // [NY][N] column j >= 1: the state arriving at node j; column 0: y(0)
+  int32_t* accepted;        // [N] steps of the interval that ends at the node (column 0: 0)
+  int32_t* rejected;        // [N]
+  int32_t* seg_status;      // [n_seg] -1: complete, else the first node of the interval that used up max_steps
+  int64_t x_off, s_off;
+  double t_fixed[2];
+  double rtol;
+  int32_t N, K, NC, n_seg, substeps, max_steps;   // substeps 0: adaptive
+  double scal[PC_MAX_SCAL];
+};
+
 #endif  // PC_ARGS_H

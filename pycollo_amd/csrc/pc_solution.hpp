@@ -408,9 +408,184 @@ __device__ __forceinline__ void sol_sample_costate(const PcSolCostateSampleArgs&
   B.out_H[i] = H;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Propagation: dy/dc = stretch (w_k / 2) f(y, u(c), q, t0, tF, s) integrated by Dormand-Prince 5(4) across
+// node intervals, u(c) the section's control interpolant (sol_legendre on coef_u, what pc_sol_sample returns).
+//
+// pc_sol_propagate_p<i>: one lane per segment [seg_node[i], seg_node[i+1]].  The lane starts from the NLP's node value,
+// walks its node intervals in order (its first section is seg_sec[i]; it moves to the next section when it reaches that
+// section's first node) and writes, at the node every interval ends at, the arriving state and the interval's step
+// counts: its own columns only.  No step straddles a node.  No LDS, no atomics; the seven stage vectors live in
+// registers (7 NY doubles), which is why a workgroup is one wave: many small workgroups spread over the CUs.
+//   fixed (substeps = m >= 1): step i of an interval starts at c_j + i h, h = (c_{j+1} - c_j) / m, and has width h (the
+//     last one: c_{j+1} - its start).  Six stages: the seventh only feeds the error estimate.
+//   adaptive (substeps = 0): h starts as the whole interval; err = max_a |e_a| / (atol_a + rtol max(|y_a|, |ynew_a|));
+//     accepted when err <= 1; factor = clamp(0.9 err^(-1/5), 0.2, 5) (5 at err = 0, at most 1 right after a rejection,
+//     0.2 when err is not finite, which rejects); next h = min(h factor, rest of the interval).  An interval that has
+//     not arrived after max_steps steps (accepted + rejected) ends the lane: seg_status = its first node, NaN from
+//     there to the segment's end.  Every loop is bounded: intervals by N, steps by max_steps or substeps (<= 2^20).
+// ---------------------------------------------------------------------------------------------
+// Dormand-Prince tableau: rows 1 .. 5 of a, row 6 = b (the fifth-order weights, also stage 7's row), e = b - b^
+__host__ __device__ constexpr double dp_a(int s, int i) {
+  constexpr double t[7][6] = {
+      {0.0, 0.0, 0.0, 0.0, 0.0, 0.0},
+      {1.0 / 5.0, 0.0, 0.0, 0.0, 0.0, 0.0},
+      {3.0 / 40.0, 9.0 / 40.0, 0.0, 0.0, 0.0, 0.0},
+      {44.0 / 45.0, -56.0 / 15.0, 32.0 / 9.0, 0.0, 0.0, 0.0},
+      {19372.0 / 6561.0, -25360.0 / 2187.0, 64448.0 / 6561.0, -212.0 / 729.0, 0.0, 0.0},
+      {9017.0 / 3168.0, -355.0 / 33.0, 46732.0 / 5247.0, 49.0 / 176.0, -5103.0 / 18656.0, 0.0},
+      {35.0 / 384.0, 0.0, 500.0 / 1113.0, 125.0 / 192.0, -2187.0 / 6784.0, 11.0 / 84.0}};
+  return t[s][i];
+}
+__host__ __device__ constexpr double dp_c(int s) {
+  constexpr double t[7] = {0.0, 1.0 / 5.0, 3.0 / 10.0, 4.0 / 5.0, 8.0 / 9.0, 1.0, 1.0};
+  return t[s];
+}
+__host__ __device__ constexpr double dp_e(int s) {
+  constexpr double t[7] = {-71.0 / 57600.0, 0.0, 71.0 / 16695.0, -71.0 / 1920.0, 17253.0 / 339200.0, -22.0 / 525.0, 1.0 / 40.0};
+  return t[s];
+}
+
+// One step of width h from (c, y) in the section whose coefficients start at off (n of them per control); g = stretch
+// w_k / 2.  v holds the q / t / s arguments of f behind NZ.  ynew: the fifth-order solution.  ERR: the seventh stage
+// and err, the scaled error norm (bad: it is not finite).
+template <class M, bool ERR>
+__device__ __forceinline__ void prop_step(const PcSolPropagateArgs& A, double* v, const double* y, int64_t off, int n, double c,
+                                          double h, double g, double* ynew, double& err, bool& bad) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NU = St::NU, NY1 = NY > 0 ? NY : 1;
+  double Ks[7][NY1];
+  static_for<0, 7>([&](auto s_) {
+    constexpr int s = decltype(s_)::value;
+    // the stage's state: y + h sum_i a[s][i] K_i, i ascending, zero entries of the tableau left out
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      double acc = 0.0;
+      static_for<0, s>([&](auto i_) {
+        constexpr int i = decltype(i_)::value;
+        constexpr double w = dp_a(s, i);
+        if constexpr (w != 0.0) acc += w * Ks[i][a];
+      });
+      v[a] = s == 0 ? y[a] : y[a] + h * acc;
+      if constexpr (s == 6) ynew[a] = v[a];
+    });
+    if constexpr (s < 6 || ERR) {
+      constexpr double cs = dp_c(s);
+      const double cc = s == 0 ? c : c + cs * h;
+      static_for<0, NU>([&](auto b_) {
+        constexpr int b = decltype(b_)::value;
+        v[NY + b] = sol_legendre(A.coef_u + (int64_t)b * A.NC + off, n, cc);
+      });
+      double F[NY1];
+      M::eval_f(v, F);
+      static_for<0, NY>([&](auto a_) { Ks[s][decltype(a_)::value] = g * F[decltype(a_)::value]; });
+    }
+  });
+  if constexpr (ERR) {
+    err = 0.0;
+    bad = false;
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      double acc = 0.0;
+      static_for<0, 7>([&](auto i_) {
+        constexpr int i = decltype(i_)::value;
+        constexpr double w = dp_e(i);
+        if constexpr (w != 0.0) acc += w * Ks[i][a];
+      });
+      const double r = fabs(h * acc) / (A.atol[a] + A.rtol * fmax(fabs(y[a]), fabs(ynew[a])));
+      if (!(r <= 1.7976931348623157e308)) bad = true;   // NaN or inf (fmax would drop a NaN)
+      err = fmax(err, r);
+    });
+  }
+}
+
+template <class M>
+__device__ __forceinline__ void sol_propagate(const PcSolPropagateArgs& A) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NY1 = NY > 0 ? NY : 1;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n_seg) return;
+  const int j0 = A.seg_node[i], j1 = A.seg_node[i + 1];
+  int k = A.seg_sec[i];
+  double t0, tF;
+  sol_times<M>(A.x, A.scal, A.x_off, A.N, A.t_fixed, t0, tF);
+  const double stretch = 0.5 * (tF - t0);
+  double v[St::NV > 0 ? St::NV : 1], y[NY1], ynew[NY1];
+  sol_params<M>(A.x, A.scal, A.x_off, A.s_off, A.N, v);
+  static_for<0, NY>([&](auto a_) {
+    constexpr int a = decltype(a_)::value;
+    y[a] = A.node_y[(int64_t)a * A.N + j0];
+    if (j0 == 0) A.y_arrive[(int64_t)a * A.N] = y[a];
+  });
+  if (j0 == 0) A.accepted[0] = A.rejected[0] = 0;
+  int status = -1;
+  for (int j = j0; j < j1; ++j) {
+    if (status >= 0) {   // behind the interval that failed
+      static_for<0, NY>([&](auto a_) { A.y_arrive[(int64_t) decltype(a_)::value * A.N + j + 1] = __builtin_nan(""); });
+      A.accepted[j + 1] = A.rejected[j + 1] = 0;
+      continue;
+    }
+    if (j >= A.sec_s[k + 1] && k < A.K - 1) ++k;
+    const int sk = A.sec_s[k], n = A.sec_s[k + 1] - sk + 1;
+    const int64_t off = (int64_t)sk + k;
+    const double ta = A.sec_tau[k], w = A.sec_tau[k + 1] - ta;
+    const double ca = 2.0 * (A.tau[j] - ta) / w - 1.0, cb = 2.0 * (A.tau[j + 1] - ta) / w - 1.0;
+    const double g = stretch * (0.5 * w);
+    int n_acc = 0, n_rej = 0;
+    double err = 0.0;
+    bool bad = false;
+    if (A.substeps > 0) {
+      const int m = A.substeps;
+      const double h = (cb - ca) / (double)m;
+      for (int q = 0; q < m; ++q) {
+        const double c = ca + (double)q * h;
+        prop_step<M, false>(A, v, y, off, n, c, q == m - 1 ? cb - c : h, g, ynew, err, bad);
+        static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
+      }
+      n_acc = m;
+    } else {
+      double c = ca, h = cb - ca;
+      bool last = true, after_reject = false, done = false;
+      while (!done && n_acc + n_rej < A.max_steps) {
+        prop_step<M, true>(A, v, y, off, n, c, h, g, ynew, err, bad);
+        double factor = 0.2;
+        if (!bad) factor = err == 0.0 ? 5.0 : fmin(5.0, fmax(0.2, 0.9 * pow(err, -0.2)));
+        if (!bad && err <= 1.0) {
+          ++n_acc;
+          static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
+          c = last ? cb : c + h;
+          if (after_reject) factor = fmin(factor, 1.0);
+          after_reject = false;
+          const double rest = cb - c;
+          if (last || !(rest > 0.0)) {
+            done = true;
+          } else {
+            h *= factor;
+            last = h >= rest;
+            if (last) h = rest;
+          }
+        } else {
+          ++n_rej;
+          h *= factor;
+          last = false;
+          after_reject = true;
+        }
+      }
+      if (!done) status = j;
+    }
+    A.accepted[j + 1] = n_acc;
+    A.rejected[j + 1] = n_rej;
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      A.y_arrive[(int64_t)a * A.N + j + 1] = status >= 0 ? __builtin_nan("") : y[a];
+    });
+  }
+  A.seg_status[i] = status;
+}
+
 }  // namespace pc
 
-// the four entry points of phase I, instantiated by the generated source once per phase
+// the five entry points of phase I, instantiated by the generated source once per phase
 #define PC_SOL_ENTRY_POINTS(I)                                                                               \
   extern "C" __global__ void __launch_bounds__(256) pc_sol_fit_p##I(PcSolFitArgs a) {                        \
     pc::sol_fit<gen::Phase##I>(a);                                                                           \
@@ -423,6 +598,9 @@ __device__ __forceinline__ void sol_sample_costate(const PcSolCostateSampleArgs&
   }                                                                                                          \
   extern "C" __global__ void __launch_bounds__(256) pc_sol_sample_costate_p##I(PcSolCostateSampleArgs a) {   \
     pc::sol_sample_costate<gen::Phase##I>(a);                                                                \
+  }                                                                                                          \
+  extern "C" __global__ void __launch_bounds__(PC_SOL_PROP_TB) pc_sol_propagate_p##I(PcSolPropagateArgs a) { \
+    pc::sol_propagate<gen::Phase##I>(a);                                                                     \
   }
 
 #endif  // PC_SOLUTION_HPP

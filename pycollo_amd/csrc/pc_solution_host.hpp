@@ -8,7 +8,11 @@
 //
 // Costates (pc_solution_set_multipliers): the index arithmetic is pc_costate_plan.hpp.  The multipliers belong to the
 // constraint and objective scaling the handle holds when they are set, which are read then.
+//
+// Propagation (pc_solution_propagate): the index arithmetic is pc_propagate_plan.hpp.  The segment list, the first
+// sections and atol are staged in buffers the solution keeps, so a device call may return before the kernel has run.
 #include "pc_costate_plan.hpp"
+#include "pc_propagate_plan.hpp"
 
 struct pc_solution {
   pc_handle* h = nullptr;
@@ -19,9 +23,11 @@ struct pc_solution {
   struct Phase {
     pcs::FitPlan plan;
     DevBuf<int32_t> sec_s, tile_k0, lane0;
-    DevBuf<double> sec_tau, node_t, node_y, node_u, node_f, coef_dy, coef_u;
+    DevBuf<double> sec_tau, node_tau, node_t, node_y, node_u, node_f, coef_dy, coef_u;
     DevBuf<double> node_p, node_H, coef_p, nu;   // costates: allocated by pc_solution_set_multipliers
-    hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr;
+    DevBuf<int32_t> prop_seg, prop_sec;          // propagation: the staged segment list and first sections,
+    DevBuf<double> prop_atol;                    // and atol
+    hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr, fn_propagate = nullptr;
     PcSolSampleArgs args;   // everything but the queries, the outputs and the flags
     int NY = 0, NU = 0, NQ = 0;
   };
@@ -53,10 +59,9 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     if (F.N != P.N) throw std::runtime_error("solution: the plan's node count differs from the handle's");
     if (D.scal_host.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
     const std::vector<double> edges = pcs::section_edges(F, tau + tau_off);
-    DevBuf<double> d_tau;
     S->tile_k0.upload(F.tile_k0);
     S->lane0.upload(F.lane0);
-    d_tau.upload(std::vector<double>(tau + tau_off, tau + tau_off + P.N));
+    S->node_tau.upload(std::vector<double>(tau + tau_off, tau + tau_off + P.N));
     tau_off += (size_t)P.N;
     S->sec_s.upload(F.sec_s);
     S->sec_tau.upload(edges);
@@ -73,7 +78,7 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     PcSolFitArgs a;
     std::memset(&a, 0, sizeof(a));
     a.x = s->d_x.p;
-    a.tau = d_tau.p;
+    a.tau = S->node_tau.p;
     a.tile_k0 = S->tile_k0.p;
     a.lane0 = S->lane0.p;
     a.sec_s = S->sec_s.p;
@@ -263,6 +268,51 @@ pc_solution::Phase& solution_phase(pc_solution* s, int phase) {
   return *s->ph[phase];
 }
 
+// pc_sol_propagate_p<phase> on the handle's stream; the outputs are device arrays ([n_y][N], [N], [N], [n_seg])
+void solution_launch_propagate(pc_solution* s, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
+                               const double* atol, int64_t max_steps, double* d_y, int32_t* d_acc, int32_t* d_rej, int32_t* d_status) {
+  auto& S = *s->ph[phase];
+  pcs::check_propagate_tolerances(substeps, rtol, atol, S.NY, max_steps);
+  const pcs::PropagatePlan P = pcs::build_propagate_plan(S.plan, n_seg, seg_nodes);
+  if (!d_acc || !d_rej || !d_status || (S.NY > 0 && !d_y)) throw std::runtime_error("propagate: null output");
+  if (!S.fn_propagate) HIP_OK(find_fn(s->h, &S.fn_propagate, ("pc_sol_propagate_p" + std::to_string(phase)).c_str()));
+  HIP_OK(hipStreamSynchronize(s->h->stream));   // an earlier call may still read the staged lists
+  S.prop_seg.upload(P.seg_node);
+  S.prop_sec.upload(P.seg_sec);
+  S.prop_atol.upload(std::vector<double>(atol, atol + S.NY));
+  PcSolPropagateArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.x = S.args.x;
+  a.tau = S.node_tau.p;
+  a.sec_s = S.sec_s.p;
+  a.sec_tau = S.sec_tau.p;
+  a.node_y = S.node_y.p;
+  a.coef_u = S.coef_u.p;
+  a.seg_node = S.prop_seg.p;
+  a.seg_sec = S.prop_sec.p;
+  a.atol = S.prop_atol.p;
+  a.y_arrive = d_y;
+  a.accepted = d_acc;
+  a.rejected = d_rej;
+  a.seg_status = d_status;
+  a.x_off = S.args.x_off;
+  a.s_off = S.args.s_off;
+  a.t_fixed[0] = S.args.t_fixed[0];
+  a.t_fixed[1] = S.args.t_fixed[1];
+  a.rtol = rtol;
+  a.N = S.plan.N;
+  a.K = S.plan.K;
+  a.NC = S.plan.NC;
+  a.n_seg = P.n_seg;
+  a.substeps = (int32_t)substeps;
+  a.max_steps = (int32_t)max_steps;
+  constexpr size_t n_scal = sizeof(a.scal) / sizeof(a.scal[0]);
+  for (size_t i = 0; i < n_scal; ++i) a.scal[i] = S.args.scal[i];
+  size_t sz = sizeof(a);
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  HIP_OK(hipModuleLaunchKernel(S.fn_propagate, (unsigned)P.blocks, 1, 1, (unsigned)P.TB, 1, 1, 0, s->h->stream, nullptr, cfg));
+}
+
 pc_solution::Phase& solution_costate_phase(pc_solution* s, int phase) {
   auto& S = solution_phase(s, phase);
   if (!s->has_costate) throw std::runtime_error("solution: no multipliers were set");
@@ -410,6 +460,39 @@ int pc_solution_sample_costate_device(pc_solution* sol, int phase, const double*
     auto& S = solution_costate_phase(sol, phase);
     if (n_t > 0 && (!d_H || (S.NY > 0 && !d_p))) throw std::runtime_error("solution: null output");
     solution_launch_sample_costate(sol, phase, d_t, n_t, flags, d_p, d_H);
+  });
+}
+
+int pc_solution_propagate(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
+                          const double* atol, int64_t max_steps, double* y_arrive, int32_t* accepted, int32_t* rejected,
+                          int32_t* seg_status) {
+  return guarded([&] {
+    auto& S = solution_phase(sol, phase);
+    if (!accepted || !rejected || !seg_status || (S.NY > 0 && !y_arrive)) throw std::runtime_error("propagate: null output");
+    if (n_seg < 1 || n_seg > (int64_t)S.plan.N - 1) throw std::runtime_error("propagate: the number of segments must be in [1, N - 1]");
+    const size_t N = (size_t)S.plan.N;
+    DevBuf<double> d_y;
+    DevBuf<int32_t> d_acc, d_rej, d_st;
+    d_y.alloc(N * (size_t)std::max(1, S.NY));
+    d_acc.alloc(N);
+    d_rej.alloc(N);
+    d_st.alloc((size_t)n_seg);
+    solution_launch_propagate(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, d_y.p, d_acc.p, d_rej.p, d_st.p);
+    HIP_OK(hipStreamSynchronize(sol->h->stream));
+    solution_down(y_arrive, d_y, N * S.NY);
+    HIP_OK(hipMemcpy(accepted, d_acc.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(rejected, d_rej.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(seg_status, d_st.p, (size_t)n_seg * sizeof(int32_t), hipMemcpyDeviceToHost));
+  });
+}
+
+int pc_solution_propagate_device(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
+                                 const double* atol, int64_t max_steps, double* d_y_arrive, int32_t* d_accepted,
+                                 int32_t* d_rejected, int32_t* d_seg_status) {
+  return guarded([&] {
+    (void)solution_phase(sol, phase);
+    solution_launch_propagate(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, d_y_arrive, d_accepted, d_rejected,
+                              d_seg_status);
   });
 }
 

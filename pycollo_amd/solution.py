@@ -44,10 +44,16 @@ W the per-OCP-row constraint scaling the handle holds.  Then:
 * Between the nodes p_a on section k is the degree n_k - 1 interpolant through the section's n_k node values, held as
   Legendre coefficients formed with the ``C_u`` table like u; H(t) is formed from the interpolated p(t) and the model
   at the interpolated (y(t), u(t)), the route by which ``sample(..., residual=True)`` forms f.
+
+Propagation (:meth:`Solution.propagate`; no reference counterpart): the dynamics integrated forward under the
+solution's control interpolant by the Dormand-Prince 5(4) pair, restarted from the NLP's own state at chosen nodes
+(``pc_sol_propagate_p<i>``, one lane per restart).  ``defect = y_arrive - state`` is what the collocation residual
+accumulates to over a node interval, a section or the whole phase.
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import functools
 
 import numpy as np
@@ -113,6 +119,63 @@ def solution_tables(method: str, n: int):
     a.setflags(write=False)
     b.setflags(write=False)
     return a, b
+
+
+PROPAGATE_MAX_STEPS = 1 << 20           # csrc/pc_args.h PC_SOL_PROP_MAX_STEPS
+
+
+@dataclasses.dataclass
+class Propagation:
+    """What :meth:`Solution.propagate` returns (NumPy arrays, or torch tensors on the device of the call's inputs).
+    ``y`` [n_y][N]: column j >= 1 is the state arriving at node j from the segment that contains the interval
+    (j - 1, j), column 0 is y(0).  ``defect`` = ``y`` - the NLP's node states; ``relative_defect`` = ``defect`` over
+    the state's scale V_a of the engine's scaling; ``terminal_defect`` [n_y]: the last column of ``defect``.
+    ``accepted`` / ``rejected`` [N]: the steps of the interval that ends at the node.  ``segments`` [n_seg + 1]: the
+    node every segment starts at, and N - 1.  ``status`` [n_seg]: -1, or the first node of the interval that used up
+    ``max_steps`` (arrivals from there to the segment's end are NaN); ``ok`` = ``status == -1``."""
+    y: object
+    defect: object
+    relative_defect: object
+    accepted: object
+    rejected: object
+    segments: np.ndarray
+    status: object
+    ok: object
+    terminal_defect: object
+
+
+def propagation_segments(restart, s, N: int) -> np.ndarray:
+    """The segment list [n_seg + 1] of ``Solution.propagate``'s ``restart``: "nodes" (every node), "sections" (the
+    section starts ``s`` [K + 1]), "phase" (one segment), or an array of node indices, which must be strictly
+    ascending from 0 to N - 1."""
+    if isinstance(restart, str):
+        if restart == "nodes":
+            return np.arange(N, dtype=np.int32)
+        if restart == "sections":
+            return np.ascontiguousarray(s, dtype=np.int32)
+        if restart == "phase":
+            return np.array([0, N - 1], dtype=np.int32)
+        raise ValueError(f'restart must be "nodes", "sections", "phase" or an array of node indices, not {restart!r}')
+    if _is_torch(restart):
+        restart = restart.detach().cpu().numpy()
+    seg = np.asarray(restart)
+    if seg.ndim != 1 or seg.size < 2 or not np.issubdtype(seg.dtype, np.integer):
+        raise ValueError("a segment list is a one-dimensional integer array of at least two node indices")
+    if seg[0] != 0 or seg[-1] != N - 1 or np.any(np.diff(seg.astype(np.int64)) <= 0):
+        raise ValueError(f"a segment list must be strictly ascending from node 0 to node {N - 1}")
+    return np.ascontiguousarray(seg, dtype=np.int32)
+
+
+def check_propagate_tolerances(substeps, rtol, atol, max_steps):
+    """The refusals of ``Solution.propagate`` (csrc/pc_propagate_plan.hpp makes the same ones)."""
+    if substeps is not None and (int(substeps) != substeps or not 1 <= substeps <= PROPAGATE_MAX_STEPS):
+        raise ValueError("substeps must be None (adaptive) or an integer in [1, 2^20]")
+    if substeps is None and not (np.isfinite(rtol) and rtol > 0):
+        raise ValueError("rtol must be finite and positive")
+    if not (np.all(np.isfinite(atol)) and np.all(atol > 0)):
+        raise ValueError("every atol must be finite and positive")
+    if int(max_steps) != max_steps or not 1 <= max_steps <= PROPAGATE_MAX_STEPS:
+        raise ValueError("max_steps must be an integer in [1, 2^20]")
 
 
 def _is_torch(t) -> bool:
@@ -260,6 +323,9 @@ class Solution:
         lib.pc_solution_costate_coefficients.argtypes = [vp, C.c_int, vp]
         lib.pc_solution_sample_costate.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp]
         lib.pc_solution_sample_costate_device.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp]
+        prop = [vp, C.c_int, C.c_int64, vp, C.c_int64, C.c_double, vp, C.c_int64, vp, vp, vp, vp]
+        lib.pc_solution_propagate.argtypes = prop
+        lib.pc_solution_propagate_device.argtypes = prop
         lib._pc_solution_declared = True
 
     def _set_multipliers(self, lam, orders):
@@ -485,3 +551,71 @@ class Solution:
         ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
         self._check(self._lib.pc_solution_sample_costate(self._h, phase, ptr(q), Q, flags, ptr(p), ptr(H)))
         return p, H
+
+    # ---- propagation -------------------------------------------------------------------------------
+    def state_scale(self, phase: int) -> np.ndarray:
+        """V_a [n_y]: the scale of every state of the phase in the engine's variable scaling (y = V y~ + r)."""
+        phase = self._phase(phase, need_handle=False)
+        pl = self.engine.layout.phases[phase]
+        V = self.engine.layout.expand_x(self.engine.V_ocp)
+        return np.array([V[pl.x_off + a * pl.N] for a in range(pl.n_y)], dtype=np.float64)
+
+    def propagate(self, phase: int, *, restart="nodes", rtol: float = 1e-9, atol=None, substeps=None, max_steps: int = 4096):
+        """Integrate the dynamics forward under the solution's controls (``pc_sol_propagate_p<i>``) and
+        return a :class:`Propagation`.
+
+        ``restart``: where the integration restarts from the NLP's own state -- "nodes" (every node: N - 1
+        independent one-interval problems, the multiple-shooting defect per interval), "sections" (every section
+        start), "phase" (one open-loop pass) or an array of node indices, strictly ascending from 0 to N - 1 (a host
+        array or a device tensor).  Inside section k the independent variable is the section variable c and
+        dy/dc = stretch (w_k / 2) f(y, u(c), q, t0, tF, s); no step straddles a node.  **u(c) is the interpolant**
+        :meth:`sample` **returns**: the degree n_k - 1 polynomial through all n_k node controls of the section.  Under
+        Radau that includes the section's end node, and in the last section the phase-final control, whatever the
+        NLP left there (no collocation row reads it).
+
+        ``substeps=m``: m equal Dormand-Prince steps per node interval, no error control (deterministic).
+        ``substeps=None``: adaptive, every interval starting with one step over the whole interval; err = max_a |e_a| /
+        (atol_a + rtol max(|y_a|, |y_a,new|)) <= 1 accepts; ``atol=None`` means rtol V_a per state (``state_scale``).
+        ``max_steps`` (accepted + rejected per interval, 1 .. 2^20) bounds the work: a segment whose interval uses it up
+        stops there (``ok`` False, NaN from that interval to the segment's end); the other segments are unaffected.
+
+        NumPy out, unless ``restart`` or ``atol`` is a torch device tensor: then torch tensors on that device.  Bad
+        arguments raise ``ValueError`` before anything is launched."""
+        phase = self._phase(phase, need_handle=False)
+        pl, mesh = self.engine.layout.phases[phase], self.engine.meshes[phase]
+        N, n_y = pl.N, pl.n_y
+        device = next((a.device for a in (restart, atol) if _is_torch(a) and a.is_cuda), None)
+        seg = propagation_segments(restart, mesh.s, N)
+        V = self.state_scale(phase)
+        if atol is None:
+            at = float(rtol) * V
+        else:
+            if _is_torch(atol):
+                atol = atol.detach().cpu().numpy()
+            at = np.ascontiguousarray(np.broadcast_to(np.asarray(atol, dtype=np.float64), (n_y,)))
+        check_propagate_tolerances(substeps, rtol, at, max_steps)
+        at = np.ascontiguousarray(at, dtype=np.float64)
+        self._phase(phase)     # (the device is needed from here on)
+        n_seg, m = len(seg) - 1, 0 if substeps is None else int(substeps)
+        head = (self._h, phase, n_seg, seg.ctypes.data, m, float(rtol), at.ctypes.data if n_y else None, int(max_steps))
+        if device is not None:
+            import torch
+            y = torch.empty((n_y, N), dtype=torch.float64, device=device)
+            acc, rej = (torch.empty((N,), dtype=torch.int32, device=device) for _ in range(2))
+            status = torch.empty((n_seg,), dtype=torch.int32, device=device)
+            torch.cuda.current_stream(device).synchronize()     # the handle's stream is not torch's
+            self._check(self._lib.pc_solution_propagate_device(*head, y.data_ptr() if n_y else None, acc.data_ptr(),
+                                                               rej.data_ptr(), status.data_ptr()))
+            self._check(self._lib.pc_synchronize(self.engine._h))
+            node_y = torch.as_tensor(np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N), device=device)
+            scale = torch.as_tensor(V, device=device)[:, None]
+        else:
+            y = np.empty((n_y, N))
+            acc, rej, status = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32), np.empty(n_seg, dtype=np.int32)
+            self._check(self._lib.pc_solution_propagate(*head, y.ctypes.data if n_y else None, acc.ctypes.data, rej.ctypes.data,
+                                                        status.ctypes.data))
+            node_y = np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N)
+            scale = V[:, None]
+        defect = y - node_y
+        return Propagation(y=y, defect=defect, relative_defect=defect / scale, accepted=acc, rejected=rej, segments=seg,
+                           status=status, ok=status == -1, terminal_defect=defect[:, -1])
