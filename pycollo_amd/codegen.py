@@ -85,6 +85,46 @@ class _Printer(C99CodePrinter):
 
 _PRINTER = _Printer({"allow_unknown_functions": False})
 
+# x^N by repeated multiplication, what _print_Pow emits for |integer powers| >= 5.  ``__device__ __forceinline__`` are
+# the HIP spellings; a host compiler that is given the printed text defines them away and gets the same function.
+POWI_PRELUDE = """template <int N> __device__ __forceinline__ double pc_powi(double x) {
+  double r = 1.0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) r *= x;
+  return r;
+}
+"""
+
+# what a model must not contain: no derivative the node functions could be differentiated through (Mod, floor,
+# ceiling), nothing SymPy left unevaluated (Derivative, Subs), nothing complex-valued, no delta function
+_REFUSED = (sym.Mod, sym.floor, sym.ceiling, sym.re, sym.im, sym.DiracDelta)
+_PRINTABLE: dict = {}    # (function class, number of arguments) -> does _Printer emit it
+
+
+def unprintable_functions(expr) -> list[str]:
+    """Names of what ``expr`` contains and the generated C cannot express, sorted; empty when it can be printed."""
+    expr = sym.sympify(expr)
+    bad = {type(a).__name__ for a in expr.atoms(sym.Derivative, sym.Subs)}
+    for a in expr.atoms(sym.Function):
+        cls = a.func
+        if isinstance(a, _REFUSED):
+            bad.add(cls.__name__)
+            continue
+        if isinstance(a, sym.Piecewise):
+            continue
+        key = (cls, len(a.args))
+        ok = _PRINTABLE.get(key)
+        if ok is None:
+            try:
+                _PRINTER.doprint(cls(*[sym.Symbol(f"a{i}", real=True) for i in range(len(a.args))], evaluate=False))
+                ok = True
+            except Exception:
+                ok = False
+            _PRINTABLE[key] = ok
+        if not ok:
+            bad.add(cls.__name__)
+    return sorted(bad)
+
 
 def _c(expr) -> str:
     return _PRINTER.doprint(sym.sympify(expr))
@@ -314,13 +354,7 @@ def generate_source(model: Model, orders=None, heavy_cap: bool | None = None, mi
              '#include "pc_kernels.hpp"',
              '#include "pc_solution.hpp"',
              "",
-             "template <int N> __device__ __forceinline__ double pc_powi(double x) {",
-             "  double r = 1.0;",
-             "#pragma unroll",
-             "  for (int i = 0; i < N; ++i) r *= x;",
-             "  return r;",
-             "}",
-             "",
+             POWI_PRELUDE,
              "namespace gen {"]
     for pm in model.phases:
         parts.append(_phase_struct(pm, model))

@@ -249,6 +249,36 @@ def _nz(e: sym.Expr) -> bool:
     return e != 0
 
 
+def _is_delta(e) -> bool:
+    return isinstance(e, sym.DiracDelta) or (isinstance(e, sym.Derivative) and isinstance(e.expr, sym.sign))
+
+
+def _diff(e: sym.Expr, var) -> sym.Expr:
+    """d e / d var almost everywhere: the derivative of a kink function (Abs, sign, Max, Min, Heaviside, a Piecewise
+    condition) is a step plus a delta function on the kink; the delta -- zero everywhere but on a set no iterate is
+    expected to hit -- is dropped, as CasADi does for fabs / fmax / fmin.  ``DiracDelta(.)`` and ``Derivative(sign(a),
+    v)`` become 0; an entry that is identically zero after that never reaches the pattern."""
+    d = sym.diff(e, var)
+    if d.has(sym.DiracDelta) or d.has(sym.Derivative):
+        d = d.replace(_is_delta, lambda *_: sym.Integer(0))
+    return d
+
+
+def _check_printable(e: sym.Expr, what: str, source: sym.Expr | None = None):
+    """Refuse here, with the user's expression named, what the code generator could only fail on later."""
+    from .codegen import unprintable_functions
+    bad = unprintable_functions(e)
+    if not bad:
+        return
+    names = ", ".join(bad)
+    if source is None:
+        raise ValueError(f"{what} uses {names}, which the generated kernels cannot evaluate or differentiate "
+                         f"(supported: see INTEGRATION.md, 'What a model may contain')")
+    used = ", ".join(sorted({type(a).__name__ for a in source.atoms(sym.Function)})) or "no function"
+    raise ValueError(f"a derivative of {what} needs {names}, which the generated kernels cannot evaluate "
+                     f"({what} uses {used}; supported: see INTEGRATION.md, 'What a model may contain')")
+
+
 _MODEL_CACHE: dict = {}    # per process: everything below depends on the equations and bounds, never on the mesh
 
 
@@ -357,6 +387,10 @@ def _compile_model(prob: _pb.ProblemSpec) -> Model:
         g_all = [lower(e, f"integrand {i}") for i, e in enumerate(ph.integrand_functions)]
         g = [e for e, nd in zip(g_all, q_need) if nd]
         F = f + p + g
+        labels = ([f"state equation {i}" for i, nd in enumerate(y_need) if nd] + [f"path constraint {i}" for i in range(len(p))]
+                  + [f"integrand {i}" for i, nd in enumerate(q_need) if nd])
+        for e, what in zip(F, labels):
+            _check_printable(e, what)
         used = set().union(*[e.free_symbols for e in F]) if F else set()
         w_syms, w_kind, w_idx = [], [], []
         for m, q_ in enumerate(q_kept):
@@ -376,8 +410,9 @@ def _compile_model(prob: _pb.ProblemSpec) -> Model:
             fs = e.free_symbols
             for c, var in enumerate(v):
                 if var in fs:
-                    d = sym.diff(e, var)
+                    d = _diff(e, var)
                     if _nz(d):
+                        _check_printable(d, labels[r], e)
                         jac.append((r, c, d))
 
         mf = [sym.Symbol(f"mf{i}", real=True) for i in range(n_y)]
@@ -392,8 +427,9 @@ def _compile_model(prob: _pb.ProblemSpec) -> Model:
             for c2 in range(c + 1):                      # lower triangle: row c >= col c2
                 var2 = v[c2]
                 if var2 in fs:
-                    d2 = sym.diff(d, var2)
+                    d2 = _diff(d, var2)
                     if _nz(d2):
+                        _check_printable(d2, labels[r], F[r])
                         key = (c, c2)
                         hess_acc[key] = hess_acc.get(key, 0) + mult[r] * d2
         hess = [(r, c, e) for (r, c), e in sorted(hess_acc.items()) if _nz(e)]
@@ -480,30 +516,37 @@ def _compile_model(prob: _pb.ProblemSpec) -> Model:
             # pycollo/backend.py:764-770
             raise ValueError(f"endpoint constraint {i} is a bare point variable; use state endpoint "
                              f"bounds instead")
-    J_grad = [(c, sym.diff(J, x)) for c, x in enumerate(xb) if x in J.free_symbols]
+    _check_printable(J, "the objective function")
+    for i, e in enumerate(b):
+        _check_printable(e, f"endpoint constraint {i}")
+    J_grad = [(c, _diff(J, x)) for c, x in enumerate(xb) if x in J.free_symbols]
     J_grad = [(c, d) for c, d in J_grad if _nz(d)]
+    for _, d in J_grad:
+        _check_printable(d, "the objective function", J)
     b_jac = []
     for r, e in enumerate(b):
         for c, x in enumerate(xb):
             if x in e.free_symbols:
-                d = sym.diff(e, x)
+                d = _diff(e, x)
                 if _nz(d):
+                    _check_printable(d, f"endpoint constraint {r}", e)
                     b_jac.append((r, c, d))
     sigma = sym.Symbol("sigma", real=True)
     lam = [sym.Symbol(f"lb{i}", real=True) for i in range(len(b))]
     hacc: dict[tuple[int, int], sym.Expr] = {}
 
-    def add_h(weight, grads):
+    def add_h(weight, grads, what, source):
         for c, d in grads:
             for c2 in range(c + 1):
                 if xb[c2] in d.free_symbols:
-                    d2 = sym.diff(d, xb[c2])
+                    d2 = _diff(d, xb[c2])
                     if _nz(d2):
+                        _check_printable(d2, what, source)
                         hacc[(c, c2)] = hacc.get((c, c2), 0) + weight * d2
 
-    add_h(sigma, J_grad)
+    add_h(sigma, J_grad, "the objective function", J)
     for r in range(len(b)):
-        add_h(lam[r], [(c, d) for rr, c, d in b_jac if rr == r])
+        add_h(lam[r], [(c, d) for rr, c, d in b_jac if rr == r], f"endpoint constraint {r}", b[r])
     pt_hess = [(r, c, e) for (r, c), e in sorted(hacc.items()) if _nz(e)]
     b_bounds = _pb._bounds_for(list(range(len(b))), prob.bounds.endpoint_constraints, "endpoint constraint") if b else []
 

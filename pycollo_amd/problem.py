@@ -138,8 +138,9 @@ class Phase:
     @state_variables.setter
     def state_variables(self, ys):
         self._y = _as_list(ys)
-        self.initial_state_variables = tuple(sym.Symbol(f"{y.name}_P{self.i}(t0)") for y in self._y)
-        self.final_state_variables = tuple(sym.Symbol(f"{y.name}_P{self.i}(tF)") for y in self._y)
+        # (an endpoint value is as real as its state: Abs, Max, ... of a real symbol differentiate to steps)
+        self.initial_state_variables = tuple(sym.Symbol(f"{y.name}_P{self.i}(t0)", **y.assumptions0) for y in self._y)
+        self.final_state_variables = tuple(sym.Symbol(f"{y.name}_P{self.i}(tF)", **y.assumptions0) for y in self._y)
 
     @property
     def control_variables(self):

@@ -609,6 +609,96 @@ def space_station(K: int = 10, order: int = 4) -> ProblemSpec:
     return prob
 
 
+def function_family(family: str, K: int = 5, order: int = 4) -> ProblemSpec:
+    """Small models whose only purpose is to send every function a model may use through the generated code: node
+    functions, their first and second partials, and the endpoint block (the objective and the endpoint constraint use
+    the family too).  Not an optimal-control problem anybody wants solved.  The bounds keep the whole box inside every
+    function's domain.  Symbols are real, as the kink family's derivatives (steps) need.
+
+    ``powers``   every branch of the power printer on each side of each cut-off: integer powers as products and as
+                 ``pc_powi``, reciprocals, half-integers up to 15/2 and past it, 1/3, a Float and a symbolic exponent;
+                 ``w`` crosses zero (negative bases, and base 0 under exponents whose derivatives stay finite), ``v``
+                 starts at 0 (half-integer exponents >= 5/2), ``u2`` is negative (negative powers of a negative base)
+    ``trig``     tan, sec, csc, cot, the inverse and hyperbolic functions, pi, E, log10; atan2 over all four quadrants
+    ``special``  erf, erfc, exp of a quadratic, log of a sum
+    ``kinks``    Abs, sign, Max, three-argument Min, Piecewise, Heaviside (derivatives almost everywhere: model.py)"""
+    R = sym.Rational
+    y, v, w, u, u2, s = sym.symbols("y v w u u2 s", real=True)
+    prob = ProblemSpec(f"Function family: {family}")
+    ph = prob.new_phase("A")
+    if family == "powers":
+        states, controls = [y, v, w], [u, u2]
+        y_b, u_b = [[0.5, 2.0], [0.0, 2.0], [-1.0, 1.0]], [[0.5, 2.0], [-3.0, -1.0]]
+        prob.parameter_variables = [s]
+        prob.bounds.parameter_variables = [[1.5, 3.5]]
+        prob.guess.parameter_variables = np.array([2.5])
+        eqs = [y**2 * u + 1 / y + sym.sqrt(y) * v + 1 / sym.sqrt(y) + w**5 + (y - R(5, 4))**5 * u,
+               y**-4 + u2**-5 + y**R(3, 2) + y**R(-3, 2) * u + v**R(5, 2) + w**4 + (y - R(5, 4))**4,
+               y**-6 * w + u2**-4 + y**R(-5, 2) + v**R(9, 2) + y**R(-9, 2) + w**8 + y**s]
+        path = [v**R(11, 2) + u**R(-11, 2) + v**R(15, 2) + u**R(-15, 2) * y + v**R(17, 2) + u2**-6 + w / u2]
+        integrand = [y**R(1, 3) + y**2.5 * u + u**y + (y**2 + v**2)**R(-9, 2) + y**4 + u**5 + w**2 * v]
+    elif family == "trig":
+        states, controls = [y, v, w], [u, u2]
+        y_b, u_b = [[0.3, 1.2], [-0.8, 0.8], [-1.0, 1.0]], [[-1.0, 1.0], [1.5, 3.0]]
+        eqs = [sym.tan(y) * u + sym.sec(y) + sym.atan2(w, u),
+               sym.csc(y) + sym.cot(y) * v + sym.asin(v) + sym.acos(v) * u,
+               sym.atan(w * u2) + sym.sinh(y) + sym.cosh(v) * w + sym.tanh(u2)]
+        path = [sym.asinh(w * u2) + sym.acosh(u2) + sym.atanh(v) * y]
+        integrand = [sym.pi * y * sym.E + sym.log(u2, 10) * v + sym.atan2(w, u) * y]
+    elif family == "special":
+        states, controls = [y, v], [u]
+        y_b, u_b = [[-1.5, 1.5], [0.5, 2.0]], [[-1.0, 1.0]]
+        eqs = [sym.erf(y) * u + sym.exp(-(y**2 + y * v + v**2 / 2)),
+               sym.erfc(y * u) + sym.log(y**2 + v + u + 2)]
+        path = [sym.erf(v * u) * y]
+        integrand = [sym.exp(-(u - y)**2) * v + sym.log(v + y**2)]
+    elif family == "kinks":
+        states, controls = [y, v], [u, u2]
+        y_b, u_b = [[-1.0, 1.0], [-1.0, 1.0]], [[-1.0, 1.0], [-1.0, 1.0]]
+        eqs = [sym.Abs(y - R(1, 4)) * u + sym.sign(v) * y**2 + sym.Max(y, v) * u2,
+               sym.Min(y, u, R(1, 2)) * v + sym.Piecewise((y**2, y > u2), (2 * y * u2 - u2**2, True)) + sym.Heaviside(v - u) * y * v]
+        path = [sym.Max(y * u, v**2) + sym.Abs(u2)]
+        integrand = [sym.Heaviside(y) * u**2 + sym.Min(y, v) * sym.Abs(v) + sym.sign(u - y) * v]
+    else:
+        raise ValueError(f"unknown function family {family!r}: powers, trig, special or kinks")
+    ph.state_variables = states
+    ph.control_variables = controls
+    ph.state_equations = eqs
+    ph.path_constraints = path
+    ph.integrand_functions = integrand
+    a0, aF, q = ph.initial_state_variables, ph.final_state_variables, ph.integral_variables[0]
+    if family == "powers":
+        prob.objective_function = q + aF[0]**-5 * aF[1]**R(5, 2) + aF[2]**6 + a0[0]**s
+        prob.endpoint_constraints = [a0[1]**R(7, 2) + aF[2]**5 + aF[0]**R(-3, 2) * a0[0]**R(1, 3) + (aF[0] - R(5, 4))**3]
+    elif family == "trig":
+        prob.objective_function = q + sym.tan(aF[0]) * sym.atan2(aF[2], a0[2]) + sym.asin(aF[1]) + sym.pi * sym.cosh(a0[1])
+        prob.endpoint_constraints = [sym.sec(a0[0]) + sym.cot(aF[0]) * sym.acos(aF[1]) + sym.atanh(a0[1]) + sym.log(aF[0], 10)]
+    elif family == "special":
+        prob.objective_function = q + sym.erf(aF[0]) * sym.exp(-aF[0] * a0[0]) + sym.erfc(a0[1])
+        prob.endpoint_constraints = [sym.log(aF[1] + a0[1] + aF[0]**2) + sym.erf(aF[0] * a0[1])]
+    else:
+        prob.objective_function = q + sym.Abs(aF[0]) * a0[1] + sym.Max(aF[0], aF[1])**2 + sym.Heaviside(a0[0]) * aF[1]**2
+        prob.endpoint_constraints = [sym.Min(aF[0], a0[1], R(1, 4)) * aF[1] + sym.sign(aF[1]) * aF[0]**2
+                                     + sym.Piecewise((aF[0] * a0[0], a0[0] > aF[1]), (aF[1] * aF[0], True))]
+    prob.bounds.endpoint_constraints = [[-1000, 1000]]
+    ph.bounds.initial_time = 0.0
+    ph.bounds.final_time = 1.0
+    ph.bounds.state_variables = y_b
+    ph.bounds.control_variables = u_b
+    ph.bounds.integral_variables = [[-100, 100]]
+    ph.bounds.path_constraints = [[-1000, 1000]]
+    mid = lambda bs: np.array([[0.5 * (lo + hi)] * 2 for lo, hi in bs])
+    ph.guess.time = np.array([0.0, 1.0])
+    ph.guess.state_variables = mid(y_b)
+    ph.guess.control_variables = mid(u_b)
+    ph.guess.integral_variables = np.array([1.0])
+    _mesh(ph, K, order)
+    return prob
+
+
+FUNCTION_FAMILIES = ("powers", "trig", "special", "kinks")
+
+
 REGISTRY = {
     "brachistochrone": brachistochrone,
     "hypersensitive": hypersensitive,
@@ -623,6 +713,7 @@ REGISTRY = {
     "free_flying_robot": free_flying_robot,
     "tumour_anti_angiogenesis": tumour_anti_angiogenesis,
     "space_station": space_station,
+    "function_family": function_family,
 }
 
 

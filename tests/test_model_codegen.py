@@ -63,6 +63,20 @@ def test_errors():
     prob.bounds.endpoint_constraints = [[0, 1]]
     with pytest.raises(ValueError, match="bare point variable"):       # backend.py:764-770
         compile_model(prob)
+    # what the printer cannot emit, or what cannot be differentiated, is refused here with the expression named --
+    # not inside generate_source, after the model was accepted (tests/test_model_functions_cpu.py: every place)
+    prob.endpoint_constraints = []
+    prob.bounds.endpoint_constraints = []
+    for fn, name in ((sym.floor, "floor"), (lambda a: sym.Mod(a, 2), "Mod"), (sym.gamma, "gamma"), (sym.Function("f"), r"\bf\b"),
+                     (sym.ceiling, "ceiling"), (sym.DiracDelta, "DiracDelta")):
+        ph.state_equations = [k * fn(y) + u]
+        with pytest.raises(ValueError, match=name) as err:
+            compile_model(prob)
+        assert "state equation 0" in str(err.value)
+    ph.state_equations = [k * sym.Abs(y) + sym.Max(y, u)]              # kinks are differentiated almost everywhere
+    m = compile_model(prob)
+    assert [(r, c) for r, c, _ in m.phases[0].hess] == []               # delta-only second partials leave the pattern
+    assert "fabs(" in codegen.generate_source(m)
 
 
 def test_digest_tracks_model():
