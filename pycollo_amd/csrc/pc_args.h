@@ -268,35 +268,52 @@ struct PcTailLaunch {   // what the host hands to pc_tail: (lead scalars..., PcT
   PcTailArgs t;
 };
 
+// What a kernel that reads a finished NLP point (pc_solution.hpp) must know about a phase to unscale it: the point, the
+// phase's place in it, its mesh and its variable scaling.  The host fills it from the handle (pc_engine.hip,
+// fill_phase_view); every argument block below embeds one.
+struct PcPhaseView {
+  const double* x;          // [num_x] scaled NLP point
+  const int32_t* sec_s;     // [K+1] first node of every section; sec_s[K] = N - 1
+  int64_t x_off, s_off;     // first x index of the phase / of the static parameters
+  double t_fixed[2];
+  int32_t N, K;
+  double scal[PC_MAX_SCAL]; // packed scaling doubles (PcPhaseArgs::scal)
+};
+
+// The polynomials of a solution (pc_solution.hpp).  A section's polynomials are held by their Legendre coefficients in
+// the section variable c in [-1, 1]; section k's n_k coefficients of a variable start at sec_s[k] + k of its row of
+// NC = N + K - 1.
+struct PcSolCurves {
+  const double* sec_tau;    // [K+1] tau at the section boundaries
+  const double* node_y;     // [NY][N] the NLP's states: where every section's integrated form starts
+  const double* coef_dy;    // [NY][NC]
+  const double* coef_u;     // [NU][NC]
+  int32_t NC, reserved;
+};
+
 // Arguments of the ph mesh-error kernel (pycollo/mesh_refinement.py:63-240).
 struct PcRefineArgs {
-  const double* x;          // [num_x] scaled solution
+  PcPhaseView v;
   const int32_t* tile_k0;   // [n_tiles+1] first section of every tile (sum of n_k+1 lanes <= blockDim)
   const int32_t* lane0;     // [K] first lane of every section inside its tile
-  const int32_t* sec_s;     // [K+1] first solution node of every section
   const double* sec_h;      // [K]
   const double* tabB;       // per order n: (n-1) x n integration of the solution-node Lagrange basis up to ph node j
   const double* tabE;       // per order n: (n-1) x n evaluation of that basis at the interior ph nodes
   const double* tabA;       // per order n: n x (n+1) integration matrix of order n+1 (quadrature A(n+1))
   double* max_rel;          // [K] section maximum of the relative error
   double* max_abs;          // [K][NY] section maximum of the absolute error per state
-  int64_t x_off, s_off;
-  double t_fixed[2];
-  int32_t N, K, tab_total_BE, tab_total_A;
+  int32_t tab_total_BE, tab_total_A;
   int32_t offBE[PC_MAX_ORDER + 1];
   int32_t offA[PC_MAX_ORDER + 1];
-  double scal[PC_MAX_SCAL];
 };
 
 // Arguments of the dense-output kernels (pc_solution.hpp; pycollo/solution/solution_abc.py:60-142,
-// casadi_solution.py:15-86).  A section's polynomials are held by their Legendre coefficients in the section variable
-// c in [-1, 1]; section k's n_k coefficients of a variable start at sec_s[k] + k of its row of NC = N + K - 1.
+// casadi_solution.py:15-86).
 struct PcSolFitArgs {
-  const double* x;          // [num_x] scaled NLP point
+  PcPhaseView v;
   const double* tau;        // [N] node abscissae
   const int32_t* tile_k0;   // [n_tiles+1] first section of every tile (sum of n_k lanes <= blockDim)
   const int32_t* lane0;     // [K] first lane of every section inside its tile
-  const int32_t* sec_s;     // [K+1] first node of every section
   const double* tabD;       // per order n: n x n, node values of f -> Legendre coefficients of the state derivative
   const double* tabU;       // per order n: n x n, node values of u -> Legendre coefficients of the control
   double* node_t;           // [N] time at the nodes
@@ -305,11 +322,8 @@ struct PcSolFitArgs {
   double* node_f;           // [NY][N] state derivatives f(y, u, q, t, s)
   double* coef_dy;          // [NY][NC]
   double* coef_u;           // [NU][NC]
-  int64_t x_off, s_off;
-  double t_fixed[2];
-  int32_t N, K, NC, tab_total;
+  int32_t NC, tab_total;
   int32_t offC[PC_MAX_ORDER + 1];
-  double scal[PC_MAX_SCAL];
 };
 
 #define PC_SOL_TAU 1          // the queries are tau in [-1, 1], not times
@@ -317,34 +331,26 @@ struct PcSolFitArgs {
 #define PC_SOL_END_SLACK 1.7763568394002505e-15   // 8 eps: a time whose tau misses [-1, 1] by no more is the phase's end
 
 struct PcSolSampleArgs {
-  const double* x;          // [num_x] scaled NLP point (free times; the q / t / s arguments of f)
+  PcPhaseView v;            // (x: the free times; the q / t / s arguments of f)
+  PcSolCurves c;
   const double* t;          // [Q] queries, any order
-  const int32_t* sec_s;     // [K+1]
-  const double* sec_tau;    // [K+1] tau at the section boundaries
-  const double* node_y;     // [NY][N]
-  const double* coef_dy;    // [NY][NC]
-  const double* coef_u;     // [NU][NC]
   double* out_y;            // [NY][Q] or null
   double* out_dy;           // [NY][Q] or null
   double* out_u;            // [NU][Q] or null
   double* out_f;            // [NY][Q] or null: f at the interpolated (y, u)
   int64_t Q;
-  int64_t x_off, s_off;
-  double t_fixed[2];
-  int32_t N, K, NC, flags;
-  double scal[PC_MAX_SCAL];
+  int32_t flags, reserved;
 };
 
 // Arguments of the costate kernels (pc_solution.hpp, "costates").  lam is the scaled multiplier vector of the whole
 // NLP, read in place: defect row r of state a of this phase is lam[c_off + a (N - 1) + r], integral row m is
 // lam[c_int_off + m].  The A tables are the (n - 1) x n integration tables of the orders in use, row-major, order n at
-// offA[n]; scal's Wd / Wi entries and wJ are the constraint and objective scaling the multipliers belong to.
+// offA[n]; v.scal's Wd / Wi entries and wJ are the constraint and objective scaling the multipliers belong to.
 struct PcSolCostateArgs {
-  const double* x;          // [num_x] scaled NLP point
+  PcPhaseView v;
   const double* lam;        // [num_c] scaled multipliers
   const int32_t* tile_k0;   // [n_tiles+1] the fit kernel's tiles
   const int32_t* lane0;     // [K]
-  const int32_t* sec_s;     // [K+1]
   const double* sec_tau;    // [K+1] tau at the section boundaries: h_k = sec_tau[k+1] - sec_tau[k]
   const double* tabA;       // per order n: (n-1) x n integration table
   const double* tabU;       // per order n: n x n, node values -> Legendre coefficients through all n nodes
@@ -352,12 +358,11 @@ struct PcSolCostateArgs {
   double* node_H;           // [N] Hamiltonian (NaN at a node without quadrature weight)
   double* coef_p;           // [NY][NC]
   double* nu;               // [NQ] integrand weights of the Hamiltonian
-  int64_t x_off, s_off, c_off, c_int_off;
+  int64_t c_off, c_int_off;
   double wJ;
-  int32_t N, K, NC, tab_total, a_total, reserved;
+  int32_t NC, tab_total, a_total, reserved;
   int32_t offC[PC_MAX_ORDER + 1];
   int32_t offA[PC_MAX_ORDER + 1];
-  double scal[PC_MAX_SCAL];
 };
 
 struct PcSolCostateSampleArgs {
@@ -373,12 +378,9 @@ struct PcSolCostateSampleArgs {
 #define PC_SOL_PROP_TB 64              // lanes of a workgroup of pc_sol_propagate
 #define PC_SOL_PROP_MAX_STEPS 1048576  // largest max_steps and largest substeps (2^20): every loop of the kernel is bounded
 struct PcSolPropagateArgs {
-  const double* x;          // [num_x] scaled NLP point (free times; the q / t / s arguments of f)
+  PcPhaseView v;            // (x: the free times; the q / t / s arguments of f)
+  PcSolCurves c;            // (node_y: where every segment starts)
   const double* tau;        // [N] node abscissae
-  const int32_t* sec_s;     // [K+1]
-  const double* sec_tau;    // [K+1] tau at the section boundaries
-  const double* node_y;     // [NY][N] the NLP's states: where every segment starts
-  const double* coef_u;     // [NU][NC]
   const int32_t* seg_node;  // [n_seg+1] segment i integrates the node intervals seg_node[i] .. seg_node[i+1]
   const int32_t* seg_sec;   // [n_seg] the section of every segment's first interval
   const double* atol;       // [NY]
@@ -386,11 +388,8 @@ struct PcSolPropagateArgs {
   int32_t* accepted;        // [N] steps of the interval that ends at the node (column 0: 0)
   int32_t* rejected;        // [N]
   int32_t* seg_status;      // [n_seg] -1: complete, else the first node of the interval that used up max_steps
-  int64_t x_off, s_off;
-  double t_fixed[2];
   double rtol;
-  int32_t N, K, NC, n_seg, substeps, max_steps;   // substeps 0: adaptive
-  double scal[PC_MAX_SCAL];
+  int32_t n_seg, substeps, max_steps, reserved;   // substeps 0: adaptive
 };
 
 #endif  // PC_ARGS_H

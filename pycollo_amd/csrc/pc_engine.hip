@@ -18,6 +18,7 @@
 #include "pc_pattern.hpp"
 #include "pc_desc.hpp"
 #include "pc_deriv.hpp"
+#include "pc_solution_plan.hpp"
 
 struct pc_deriv_dev;   // (pc_deriv_check.hpp: the derivative check's device buffers)
 struct pc_kkt;   // (pc_kkt.hip; the interior-point state below drives it through the exported calls)
@@ -341,6 +342,34 @@ void fill_phase_args(pc_handle* h, size_t ip, PcPhaseArgs& a, const double* d_x,
   a.qw_total = (int32_t)h->qw.size();
   std::memcpy(a.qa_off, h->qa_off, sizeof(a.qa_off));
   std::memcpy(a.qw_off, h->qw_off, sizeof(a.qw_off));
+}
+
+// What the kernels that read a finished NLP point (pc_solution.hpp) know about a phase: the point d_x, the phase's place
+// in it, its mesh and the variable scaling the handle holds now.
+PcPhaseView fill_phase_view(pc_handle* h, int phase, const double* d_x) {
+  auto& P = h->Q.ph[phase];
+  auto& D = *h->pd[phase];
+  if (D.scal_host.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
+  PcPhaseView v;
+  std::memset(&v, 0, sizeof(v));
+  v.x = d_x;
+  v.sec_s = D.sec_s.p;
+  v.x_off = P.x_off;
+  v.s_off = h->Q.s_off;
+  v.t_fixed[0] = P.t_fixed[0];
+  v.t_fixed[1] = P.t_fixed[1];
+  v.N = P.N;
+  v.K = P.K;
+  for (size_t i = 0; i < D.scal_host.size(); ++i) v.scal[i] = D.scal_host[i];
+  return v;
+}
+
+// one kernel whose parameter is the argument block `args`, passed by value
+template <class Args>
+void launch_block(hipFunction_t fn, unsigned grid, unsigned block, size_t lds, hipStream_t stream, Args& args) {
+  size_t sz = sizeof(args);
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  HIP_OK(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, (unsigned)lds, stream, nullptr, cfg));
 }
 
 void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_c, double* d_G, double* d_H,
@@ -1675,75 +1704,40 @@ int pc_mesh_error(pc_handle* h, int phase, const double* x, int n_orders, const 
     hipFunction_t fn = nullptr;
     const std::string name = "pc_mesh_err_p" + std::to_string(phase);
     HIP_OK(find_fn(h, &fn, name.c_str()));
-    PcRefineArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (int i = 0; i <= PC_MAX_ORDER; ++i) a.offBE[i] = a.offA[i] = -1;
-    size_t oBE = 0, oA = 0;
-    for (int i = 0; i < n_orders; ++i) {
-      const int n = orders[i];
-      if (n < 2 || n >= PC_MAX_ORDER) throw std::runtime_error("mesh-error tables: order outside [2, 19]");
-      a.offBE[n] = (int32_t)oBE;
-      a.offA[n] = (int32_t)oA;
-      oBE += (size_t)(n - 1) * n;
-      oA += (size_t)n * (n + 1);
-    }
-    for (int k = 0; k < P.K; ++k)
-      if (a.offBE[P.n_k[k]] < 0) throw std::runtime_error("mesh-error tables: an order in use has no table");
-    // tiles: every section occupies n_k + 1 lanes
-    const int TB = 256;
-    std::vector<int32_t> tile_k0{0}, lane0(P.K);
-    int lanes = 0;
-    for (int k = 0; k < P.K; ++k) {
-      const int need = P.n_k[k] + 1;
-      if (lanes + need > TB) {
-        tile_k0.push_back(k);
-        lanes = 0;
-      }
-      lane0[k] = lanes;
-      lanes += need;
-    }
-    tile_k0.push_back(P.K);
+    const pcs::MeshErrorPlan M =
+        pcs::build_mesh_error_plan(P.K, P.n_k.data(), n_orders, orders, P.n_y, P.n_u, 256, h->lds_limit);
     DevBuf<int32_t> d_tile, d_lane;
     DevBuf<double> d_B, d_E, d_A, d_rel, d_abs;
-    d_tile.upload(tile_k0);
-    d_lane.upload(lane0);
-    d_B.upload(std::vector<double>(tabB, tabB + oBE));
-    d_E.upload(std::vector<double>(tabE, tabE + oBE));
-    d_A.upload(std::vector<double>(tabA, tabA + oA));
+    d_tile.upload(M.tile_k0);
+    d_lane.upload(M.lane0);
+    d_B.upload(std::vector<double>(tabB, tabB + M.tab_total_BE));
+    d_E.upload(std::vector<double>(tabE, tabE + M.tab_total_BE));
+    d_A.upload(std::vector<double>(tabA, tabA + M.tab_total_A));
     d_rel.alloc(P.K);
     d_abs.alloc((size_t)P.K * std::max(1, P.n_y));
     // (always through the device mirror; the callback cache no longer describes it afterwards)
     std::memcpy(h->h_in.p, x, Q.num_x * sizeof(double));
     HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in.p, Q.num_x * sizeof(double), hipMemcpyHostToDevice, h->stream));
     h->x_valid = h->fc_valid = false;
-    a.x = h->d_in.p;
+    PcRefineArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.v = fill_phase_view(h, phase, h->d_in.p);
     a.tile_k0 = d_tile.p;
     a.lane0 = d_lane.p;
-    a.sec_s = D.sec_s.p;
     a.sec_h = D.sec_h.p;
     a.tabB = d_B.p;
     a.tabE = d_E.p;
     a.tabA = d_A.p;
     a.max_rel = d_rel.p;
     a.max_abs = d_abs.p;
-    a.x_off = P.x_off;
-    a.s_off = Q.s_off;
-    a.t_fixed[0] = P.t_fixed[0];
-    a.t_fixed[1] = P.t_fixed[1];
-    a.N = P.N;
-    a.K = P.K;
-    a.tab_total_BE = (int32_t)oBE;
-    a.tab_total_A = (int32_t)oA;
-    for (size_t i = 0; i < D.scal_host.size(); ++i) a.scal[i] = D.scal_host[i];
-    const int NU = P.n_u, NY = P.n_y;
-    const size_t lds = 8 * (2 * oBE + oA + (size_t)TB * (5 * NY + std::max(1, NU) + 1)) + 4 * (size_t)TB;
-    if ((int)lds > h->lds_limit) throw std::runtime_error("mesh-error kernel: tables do not fit in LDS");
-    size_t sz = sizeof(a);
-    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-    HIP_OK(hipModuleLaunchKernel(fn, (int)tile_k0.size() - 1, 1, 1, TB, 1, 1, (unsigned)lds, h->stream, nullptr, cfg));
+    a.tab_total_BE = M.tab_total_BE;
+    a.tab_total_A = M.tab_total_A;
+    std::memcpy(a.offBE, M.offBE, sizeof(a.offBE));
+    std::memcpy(a.offA, M.offA, sizeof(a.offA));
+    launch_block(fn, M.n_tiles(), M.TB, M.lds_bytes, h->stream, a);
     HIP_OK(hipStreamSynchronize(h->stream));
     HIP_OK(hipMemcpy(max_rel, d_rel.p, sizeof(double) * P.K, hipMemcpyDeviceToHost));
-    if (max_abs && NY > 0) HIP_OK(hipMemcpy(max_abs, d_abs.p, sizeof(double) * (size_t)P.K * NY, hipMemcpyDeviceToHost));
+    if (max_abs && P.n_y > 0) HIP_OK(hipMemcpy(max_abs, d_abs.p, sizeof(double) * (size_t)P.K * P.n_y, hipMemcpyDeviceToHost));
   });
 }
 

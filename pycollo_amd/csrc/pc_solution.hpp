@@ -1,4 +1,5 @@
-// Dense output of an NLP point (pycollo/solution/solution_abc.py:60-142, casadi_solution.py:15-86): device side.
+// Kernels that read a finished NLP point: the dense output (pycollo/solution/solution_abc.py:60-142,
+// casadi_solution.py:15-86), the costates, the propagation and the ph mesh-error estimate.
 // Included by the generated code object after pc_kernels.hpp (S<M>, static_for, M::eval_f).
 //
 // Per section k (n nodes, section variable c in [-1, 1]):
@@ -11,29 +12,82 @@
 
 namespace pc {
 
+// ---- what the kernels share: unscaling through the phase view, the lanes of a tile, the table contraction ----
 template <class M>
-__device__ __forceinline__ void sol_times(const double* __restrict__ x, const double* sc, int64_t x_off, int N,
-                                          const double* t_fixed, double& t0, double& tF) {
+__device__ __forceinline__ void sol_times(const PcPhaseView& V, double& t0, double& tF) {
   using St = S<M>;
-  t0 = t_fixed[0];
-  tF = t_fixed[1];
-  const int64_t t_off = x_off + (int64_t)St::NZ * N + St::NQ;
+  const double* sc = V.scal;
+  t0 = V.t_fixed[0];
+  tF = V.t_fixed[1];
+  const int64_t t_off = V.x_off + (int64_t)St::NZ * V.N + St::NQ;
   int j = 0;
-  if constexpr (M::T0_FREE) { t0 = sc[St::O_VT + j] * x[t_off + j] + sc[St::O_RT + j]; ++j; }
-  if constexpr (M::TF_FREE) { tF = sc[St::O_VT + j] * x[t_off + j] + sc[St::O_RT + j]; }
+  if constexpr (M::T0_FREE) { t0 = sc[St::O_VT + j] * V.x[t_off + j] + sc[St::O_RT + j]; ++j; }
+  if constexpr (M::TF_FREE) { tF = sc[St::O_VT + j] * V.x[t_off + j] + sc[St::O_RT + j]; }
 }
 
 // the q / t / s arguments of f, unscaled, into v[NZ ..]
 template <class M>
-__device__ __forceinline__ void sol_params(const double* __restrict__ x, const double* sc, int64_t x_off, int64_t s_off,
-                                           int N, double* v) {
+__device__ __forceinline__ void sol_params(const PcPhaseView& V, double* v) {
   using St = S<M>;
+  const double* sc = V.scal;
   static_for<0, St::NS>([&](auto l_) {
     constexpr int l = decltype(l_)::value;
     constexpr int kind = M::wk(l), idx = M::wi(l);   // static parameter, or this phase's q / free t
-    const int64_t col = kind == 0 ? s_off + idx : x_off + (int64_t)St::NZ * N + (kind == 1 ? idx : St::NQ + idx);
-    v[St::NZ + l] = sc[St::O_VS + l] * x[col] + sc[St::O_RS + l];
+    const int64_t col = kind == 0 ? V.s_off + idx : V.x_off + (int64_t)St::NZ * V.N + (kind == 1 ? idx : St::NQ + idx);
+    v[St::NZ + l] = sc[St::O_VS + l] * V.x[col] + sc[St::O_RS + l];
   });
+}
+
+// the states and controls of a node, unscaled, into v[0 .. NZ)
+template <class M>
+__device__ __forceinline__ void sol_node(const PcPhaseView& V, int node, double* v) {
+  using St = S<M>;
+  const double* sc = V.scal;
+  static_for<0, St::NZ>([&](auto b_) {
+    constexpr int b = decltype(b_)::value;
+    v[b] = sc[St::O_VZ + b] * V.x[V.x_off + (int64_t)b * V.N + node] + sc[St::O_RZ + b];
+  });
+}
+
+// The tile of a workgroup is the run of sections k0 .. k1 (tile_k0[blockIdx.x], tile_k0[blockIdx.x + 1]); section k owns
+// the n_k + extra consecutive lanes from lane0[k] (the host's pcs::section_tiles).  Which section a lane belongs to goes
+// through s_sec [blockDim].  Returned: the lane's section k, its first node sk, its nodes n, its first lane l0 and the
+// lane's place j in it; a lane beyond the tile's last section is not active.  Two barriers: what the kernel staged
+// before the call is visible after it.
+struct SolLane {
+  int k, sk, n, l0, j;
+  bool active;
+};
+__device__ __forceinline__ SolLane sol_lane_map(const PcPhaseView& V, int k0, int k1, const int32_t* lane0, int extra,
+                                                int* s_sec) {
+  const int tid = threadIdx.x, TB = blockDim.x;
+  s_sec[tid] = -1;
+  __syncthreads();
+  for (int k = k0 + tid; k < k1; k += TB) {
+    const int lanes = V.sec_s[k + 1] - V.sec_s[k] + 1 + extra, l0 = lane0[k];
+    for (int j = 0; j < lanes; ++j)
+      if (l0 + j < TB) s_sec[l0 + j] = k;
+  }
+  __syncthreads();
+  SolLane L;
+  L.k = s_sec[tid];
+  L.active = L.k >= 0;
+  const int kc = L.active ? L.k : k0;   // (a lane without a section reads the tile's first: its values are not used)
+  L.sk = V.sec_s[kc];
+  L.n = V.sec_s[kc + 1] - L.sk + 1;
+  L.l0 = lane0[kc];
+  L.j = tid - L.l0;
+  return L;
+}
+
+// a node shared by two sections is written by the section it opens (the last node: by the last section)
+__device__ __forceinline__ bool sol_owner(const SolLane& L, int K) { return L.j < L.n - 1 || L.k == K - 1; }
+
+// row . vals over n entries, ascending: a lane's row of a section table against the section's staged values
+__device__ __forceinline__ double sol_row_dot(const double* row, const double* vals, int n) {
+  double acc = 0.0;
+  for (int i = 0; i < n; ++i) acc += row[i] * vals[i];
+  return acc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -45,79 +99,55 @@ __device__ __forceinline__ void sol_params(const double* __restrict__ x, const d
 template <class M>
 __device__ __forceinline__ void sol_fit(const PcSolFitArgs& A) {
   using St = S<M>;
-  constexpr int NY = St::NY, NU = St::NU, NZ = St::NZ;
+  constexpr int NY = St::NY, NU = St::NU;
   extern __shared__ double smem[];
   const int tid = threadIdx.x, TB = blockDim.x;
+  const PcPhaseView& V = A.v;
   double* s_D = smem;
   double* s_U = s_D + A.tab_total;
   double* s_f = s_U + A.tab_total;                  // [NY][TB]
   double* s_u = s_f + (NY > 0 ? NY : 1) * TB;       // [NU][TB]
   int* s_sec = reinterpret_cast<int*>(s_u + (NU > 0 ? NU : 1) * TB);   // [TB] section of every lane
-  const int k0 = A.tile_k0[blockIdx.x], k1 = A.tile_k0[blockIdx.x + 1];
   for (int i = tid; i < A.tab_total; i += TB) {
     s_D[i] = A.tabD[i];
     s_U[i] = A.tabU[i];
   }
-  s_sec[tid] = -1;
-  __syncthreads();
-  for (int k = k0 + tid; k < k1; k += TB) {
-    const int n = A.sec_s[k + 1] - A.sec_s[k] + 1, l0 = A.lane0[k];
-    for (int j = 0; j < n; ++j)
-      if (l0 + j < TB) s_sec[l0 + j] = k;
-  }
-  __syncthreads();
-  const int k = s_sec[tid];
-  const bool active = k >= 0;
-  const double* sc = A.scal;
+  const SolLane L = sol_lane_map(V, A.tile_k0[blockIdx.x], A.tile_k0[blockIdx.x + 1], A.lane0, 0, s_sec);
   double t0, tF;
-  sol_times<M>(A.x, sc, A.x_off, A.N, A.t_fixed, t0, tF);
-  int n = 2, j = 0, l0 = 0, sk = 0;
-  if (active) {
-    sk = A.sec_s[k];
-    n = A.sec_s[k + 1] - sk + 1;
-    l0 = A.lane0[k];
-    j = tid - l0;
-    const int node = sk + j;
+  sol_times<M>(V, t0, tF);
+  if (L.active) {
+    const int node = L.sk + L.j;
     double v[St::NV > 0 ? St::NV : 1], F[NY > 0 ? NY : 1];
-    sol_params<M>(A.x, sc, A.x_off, A.s_off, A.N, v);
-    static_for<0, NZ>([&](auto b_) {
-      constexpr int b = decltype(b_)::value;
-      v[b] = sc[St::O_VZ + b] * A.x[A.x_off + (int64_t)b * A.N + node] + sc[St::O_RZ + b];
-    });
+    sol_params<M>(V, v);
+    sol_node<M>(V, node, v);
     M::eval_f(v, F);
-    // a node shared by two sections is written by the section it opens (the last node: by the last section)
-    const bool owner = j < n - 1 || k == A.K - 1;
+    const bool owner = sol_owner(L, V.K);
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
       s_f[a * TB + tid] = F[a];
       if (owner) {
-        A.node_y[(int64_t)a * A.N + node] = v[a];
-        A.node_f[(int64_t)a * A.N + node] = F[a];
+        A.node_y[(int64_t)a * V.N + node] = v[a];
+        A.node_f[(int64_t)a * V.N + node] = F[a];
       }
     });
     static_for<0, NU>([&](auto b_) {
       constexpr int b = decltype(b_)::value;
       s_u[b * TB + tid] = v[NY + b];
-      if (owner) A.node_u[(int64_t)b * A.N + node] = v[NY + b];
+      if (owner) A.node_u[(int64_t)b * V.N + node] = v[NY + b];
     });
     if (owner) A.node_t[node] = A.tau[node] * (0.5 * (tF - t0)) + 0.5 * (t0 + tF);   // casadi_solution.py:80-83
   }
   __syncthreads();
-  if (active) {
-    const double* Dr = s_D + A.offC[n] + j * n;
-    const double* Ur = s_U + A.offC[n] + j * n;
-    const int64_t slot = (int64_t)sk + k + j;
+  if (L.active) {
+    const int n = L.n, row = A.offC[n] + L.j * n;
+    const int64_t slot = (int64_t)L.sk + L.k + L.j;
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
-      double acc = 0.0;
-      for (int i = 0; i < n; ++i) acc += Dr[i] * s_f[a * TB + l0 + i];
-      A.coef_dy[(int64_t)a * A.NC + slot] = acc;
+      A.coef_dy[(int64_t)a * A.NC + slot] = sol_row_dot(s_D + row, s_f + a * TB + L.l0, n);
     });
     static_for<0, NU>([&](auto b_) {
       constexpr int b = decltype(b_)::value;
-      double acc = 0.0;
-      for (int i = 0; i < n; ++i) acc += Ur[i] * s_u[b * TB + l0 + i];
-      A.coef_u[(int64_t)b * A.NC + slot] = acc;
+      A.coef_u[(int64_t)b * A.NC + slot] = sol_row_dot(s_U + row, s_u + b * TB + L.l0, n);
     });
   }
 }
@@ -140,7 +170,7 @@ struct SolSpot {
 template <class M>
 __device__ __forceinline__ bool sol_locate(const PcSolSampleArgs& A, int64_t i, SolSpot& s) {
   double t0, tF;
-  sol_times<M>(A.x, A.scal, A.x_off, A.N, A.t_fixed, t0, tF);
+  sol_times<M>(A.v, t0, tF);
   const double stretch = 0.5 * (tF - t0), shift = 0.5 * (t0 + tF);
   const double q = A.t[i];
   double tau;
@@ -157,16 +187,16 @@ __device__ __forceinline__ bool sol_locate(const PcSolSampleArgs& A, int64_t i, 
   }
   if (!(inside || ((A.flags & PC_SOL_EXTRAPOLATE) && tau == tau))) return false;
   // the last boundary <= tau, kept inside [0, K - 1]
-  int lo = 0, hi = A.K;
+  int lo = 0, hi = A.v.K;
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
-    if (A.sec_tau[mid] <= tau) lo = mid; else hi = mid;
+    if (A.c.sec_tau[mid] <= tau) lo = mid; else hi = mid;
   }
   s.k = lo;
-  s.sk = A.sec_s[lo];
-  s.n = A.sec_s[lo + 1] - s.sk + 1;
-  const double ta = A.sec_tau[lo];
-  s.w = A.sec_tau[lo + 1] - ta;
+  s.sk = A.v.sec_s[lo];
+  s.n = A.v.sec_s[lo + 1] - s.sk + 1;
+  const double ta = A.c.sec_tau[lo];
+  s.w = A.c.sec_tau[lo + 1] - ta;
   s.c = 2.0 * (tau - ta) / s.w - 1.0;
   s.stretch = stretch;
   s.off = (int64_t)s.sk + lo;
@@ -175,7 +205,7 @@ __device__ __forceinline__ bool sol_locate(const PcSolSampleArgs& A, int64_t i, 
 
 // state a at the spot (the integrated form) and, in d, its derivative
 __device__ __forceinline__ double sol_state(const PcSolSampleArgs& A, const SolSpot& s, int a, double& d) {
-  const double* cf = A.coef_dy + (int64_t)a * A.NC + s.off;
+  const double* cf = A.c.coef_dy + (int64_t)a * A.c.NC + s.off;
   const double c = s.c;
   // j = n .. 0: b_j = a_(j-1) / (2j - 1) - a_(j+1) / (2j + 3) are the coefficients of int_{-1}^{c} ydot
   // (b_0 = a_0 - a_1 / 3); ydot's own Clenshaw step j uses a_j
@@ -195,7 +225,7 @@ __device__ __forceinline__ double sol_state(const PcSolSampleArgs& A, const SolS
     a_mid = a_lo;
   }
   d = d1;
-  return A.node_y[(int64_t)a * A.N + s.sk] + s.stretch * ((0.5 * s.w) * y1);
+  return A.c.node_y[(int64_t)a * A.v.N + s.sk] + s.stretch * ((0.5 * s.w) * y1);
 }
 
 // sum_j cf[j] P_j(c), j < n (Clenshaw): the controls, the costates
@@ -241,12 +271,12 @@ __device__ __forceinline__ void sol_sample(const PcSolSampleArgs& A) {
   });
   static_for<0, NU>([&](auto b_) {
     constexpr int b = decltype(b_)::value;
-    const double u = sol_legendre(A.coef_u + (int64_t)b * A.NC + s.off, s.n, s.c);
+    const double u = sol_legendre(A.c.coef_u + (int64_t)b * A.c.NC + s.off, s.n, s.c);
     v[NY + b] = u;
     if (A.out_u) A.out_u[(int64_t)b * A.Q + i] = u;
   });
   if (A.out_f) {
-    sol_params<M>(A.x, A.scal, A.x_off, A.s_off, A.N, v);
+    sol_params<M>(A.v, v);
     M::eval_f(v, F);
     static_for<0, NY>([&](auto a_) { A.out_f[(int64_t) decltype(a_)::value * A.Q + i] = F[decltype(a_)::value]; });
   }
@@ -271,51 +301,38 @@ __device__ __forceinline__ void sol_sample(const PcSolSampleArgs& A) {
 template <class M>
 __device__ __forceinline__ void sol_costate(const PcSolCostateArgs& A) {
   using St = S<M>;
-  constexpr int NY = St::NY, NZ = St::NZ, NQ = St::NQ;
+  constexpr int NY = St::NY, NQ = St::NQ;
   constexpr int NY1 = NY > 0 ? NY : 1, NQ1 = NQ > 0 ? NQ : 1;
   extern __shared__ double smem[];
   const int tid = threadIdx.x, TB = blockDim.x, LW = PC_SOL_LAM_ROWS(TB);
+  const PcPhaseView& V = A.v;
   double* s_U = smem;
   double* s_A = s_U + A.tab_total;
   double* s_lam = s_A + A.a_total;                   // [NY][LW] Lam of rows r_lo ..
   double* s_p = s_lam + NY1 * LW;                    // [NY][TB]
   int* s_sec = reinterpret_cast<int*>(s_p + NY1 * TB);   // [TB] section of every lane
   const int k0 = A.tile_k0[blockIdx.x], k1 = A.tile_k0[blockIdx.x + 1];
-  const double* sc = A.scal;
+  const double* sc = V.scal;
   for (int i = tid; i < A.tab_total; i += TB) s_U[i] = A.tabU[i];
   for (int i = tid; i < A.a_total; i += TB) s_A[i] = A.tabA[i];
   // rows of the tile's sections and of the sections before and after it
-  const int r_lo = A.sec_s[k0 > 0 ? k0 - 1 : 0], r_hi = A.sec_s[k1 < A.K ? k1 + 1 : A.K];
+  const int r_lo = V.sec_s[k0 > 0 ? k0 - 1 : 0], r_hi = V.sec_s[k1 < V.K ? k1 + 1 : V.K];
   static_for<0, NY>([&](auto a_) {
     constexpr int a = decltype(a_)::value;
-    const double* la = A.lam + A.c_off + (int64_t)a * (A.N - 1) + r_lo;
+    const double* la = A.lam + A.c_off + (int64_t)a * (V.N - 1) + r_lo;
     for (int i = tid; i < r_hi - r_lo && i < LW; i += TB) s_lam[a * LW + i] = sc[St::O_WD + a] * la[i] / A.wJ;
   });
-  s_sec[tid] = -1;
-  __syncthreads();
-  for (int k = k0 + tid; k < k1; k += TB) {
-    const int n = A.sec_s[k + 1] - A.sec_s[k] + 1, l0 = A.lane0[k];
-    for (int j = 0; j < n; ++j)
-      if (l0 + j < TB) s_sec[l0 + j] = k;
-  }
-  __syncthreads();
-  const int k = s_sec[tid];
-  const bool active = k >= 0;
-  int n = 2, j = 0, l0 = 0, sk = 0;
-  if (active) {
-    sk = A.sec_s[k];
-    n = A.sec_s[k + 1] - sk + 1;
-    l0 = A.lane0[k];
-    j = tid - l0;
-    const int node = sk + j;
+  const SolLane L = sol_lane_map(V, k0, k1, A.lane0, 0, s_sec);
+  if (L.active) {
+    const int k = L.k, n = L.n, j = L.j, node = L.sk + j;
     // the sections of the node: [ka, kb], positions pa (in ka) and 0 (in kb > ka)
     int ka = k, pa = j, kb = k;
-    if (j == 0 && k > 0) { ka = k - 1; pa = sk - A.sec_s[k - 1]; }
-    if (j == n - 1 && k < A.K - 1) kb = k + 1;
+    if (j == 0 && k > 0) { ka = k - 1; pa = L.sk - V.sec_s[k - 1]; }
+    if (j == n - 1 && k < V.K - 1) kb = k + 1;
     double omega = 0.0, num[NY1];
     static_for<0, NY>([&](auto a_) { num[decltype(a_)::value] = 0.0; });
     for (int kk = ka; kk <= kb; ++kk) {
-      const int s0 = A.sec_s[kk], nn = A.sec_s[kk + 1] - s0 + 1, pos = kk == ka ? pa : 0;
+      const int s0 = V.sec_s[kk], nn = V.sec_s[kk + 1] - s0 + 1, pos = kk == ka ? pa : 0;
       const double h = A.sec_tau[kk + 1] - A.sec_tau[kk];
       const double* At = s_A + A.offA[nn] + pos;
       omega += h * At[(nn - 2) * nn];
@@ -328,17 +345,14 @@ __device__ __forceinline__ void sol_costate(const PcSolCostateArgs& A) {
       });
     }
     double v[St::NV > 0 ? St::NV : 1], F[NY1], G[NQ1], p[NY1];
-    sol_params<M>(A.x, sc, A.x_off, A.s_off, A.N, v);
-    static_for<0, NZ>([&](auto b_) {
-      constexpr int b = decltype(b_)::value;
-      v[b] = sc[St::O_VZ + b] * A.x[A.x_off + (int64_t)b * A.N + node] + sc[St::O_RZ + b];
-    });
+    sol_params<M>(V, v);
+    sol_node<M>(V, node, v);
     M::eval_fg(v, F, G);
-    const bool weighted = !(node == A.N - 1 && omega == 0.0);   // (the tile of node N - 1 stages row N - 2)
+    const bool weighted = !(node == V.N - 1 && omega == 0.0);   // (the tile of node N - 1 stages row N - 2)
     double H = 0.0;
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
-      p[a] = weighted ? num[a] / omega : s_lam[a * LW + (A.N - 2 - r_lo)];
+      p[a] = weighted ? num[a] / omega : s_lam[a * LW + (V.N - 2 - r_lo)];
       H += p[a] * F[a];
     });
     static_for<0, NQ>([&](auto m_) {
@@ -347,23 +361,22 @@ __device__ __forceinline__ void sol_costate(const PcSolCostateArgs& A) {
       H += nu * G[m];
       if (blockIdx.x == 0 && tid == 0) A.nu[m] = nu;
     });
-    const bool owner = j < n - 1 || k == A.K - 1;
+    const bool owner = sol_owner(L, V.K);
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
       s_p[a * TB + tid] = p[a];
-      if (owner) A.node_p[(int64_t)a * A.N + node] = p[a];
+      if (owner) A.node_p[(int64_t)a * V.N + node] = p[a];
     });
     if (owner) A.node_H[node] = weighted ? H : __builtin_nan("");
   }
   __syncthreads();
-  if (active) {
-    const double* Ur = s_U + A.offC[n] + j * n;
-    const int64_t slot = (int64_t)sk + k + j;
+  if (L.active) {
+    const int n = L.n;
+    const double* Ur = s_U + A.offC[n] + L.j * n;
+    const int64_t slot = (int64_t)L.sk + L.k + L.j;
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
-      double acc = 0.0;
-      for (int i = 0; i < n; ++i) acc += Ur[i] * s_p[a * TB + l0 + i];
-      A.coef_p[(int64_t)a * A.NC + slot] = acc;
+      A.coef_p[(int64_t)a * A.NC + slot] = sol_row_dot(Ur, s_p + a * TB + L.l0, n);
     });
   }
 }
@@ -393,14 +406,14 @@ __device__ __forceinline__ void sol_sample_costate(const PcSolCostateSampleArgs&
   });
   static_for<0, NU>([&](auto b_) {
     constexpr int b = decltype(b_)::value;
-    v[NY + b] = sol_legendre(A.coef_u + (int64_t)b * A.NC + s.off, s.n, s.c);
+    v[NY + b] = sol_legendre(A.c.coef_u + (int64_t)b * A.c.NC + s.off, s.n, s.c);
   });
-  sol_params<M>(A.x, A.scal, A.x_off, A.s_off, A.N, v);
+  sol_params<M>(A.v, v);
   M::eval_fg(v, F, G);
   double H = 0.0;
   static_for<0, NY>([&](auto a_) {
     constexpr int a = decltype(a_)::value;
-    const double p = sol_legendre(B.coef_p + (int64_t)a * A.NC + s.off, s.n, s.c);
+    const double p = sol_legendre(B.coef_p + (int64_t)a * A.c.NC + s.off, s.n, s.c);
     B.out_p[(int64_t)a * A.Q + i] = p;
     H += p * F[a];
   });
@@ -474,7 +487,7 @@ __device__ __forceinline__ void prop_step(const PcSolPropagateArgs& A, double* v
       const double cc = s == 0 ? c : c + cs * h;
       static_for<0, NU>([&](auto b_) {
         constexpr int b = decltype(b_)::value;
-        v[NY + b] = sol_legendre(A.coef_u + (int64_t)b * A.NC + off, n, cc);
+        v[NY + b] = sol_legendre(A.c.coef_u + (int64_t)b * A.c.NC + off, n, cc);
       });
       double F[NY1];
       M::eval_f(v, F);
@@ -505,30 +518,32 @@ __device__ __forceinline__ void sol_propagate(const PcSolPropagateArgs& A) {
   constexpr int NY = St::NY, NY1 = NY > 0 ? NY : 1;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= A.n_seg) return;
+  const int N = A.v.N;
+  const int32_t* sec_s = A.v.sec_s;
   const int j0 = A.seg_node[i], j1 = A.seg_node[i + 1];
   int k = A.seg_sec[i];
   double t0, tF;
-  sol_times<M>(A.x, A.scal, A.x_off, A.N, A.t_fixed, t0, tF);
+  sol_times<M>(A.v, t0, tF);
   const double stretch = 0.5 * (tF - t0);
   double v[St::NV > 0 ? St::NV : 1], y[NY1], ynew[NY1];
-  sol_params<M>(A.x, A.scal, A.x_off, A.s_off, A.N, v);
+  sol_params<M>(A.v, v);
   static_for<0, NY>([&](auto a_) {
     constexpr int a = decltype(a_)::value;
-    y[a] = A.node_y[(int64_t)a * A.N + j0];
-    if (j0 == 0) A.y_arrive[(int64_t)a * A.N] = y[a];
+    y[a] = A.c.node_y[(int64_t)a * N + j0];
+    if (j0 == 0) A.y_arrive[(int64_t)a * N] = y[a];
   });
   if (j0 == 0) A.accepted[0] = A.rejected[0] = 0;
   int status = -1;
   for (int j = j0; j < j1; ++j) {
     if (status >= 0) {   // behind the interval that failed
-      static_for<0, NY>([&](auto a_) { A.y_arrive[(int64_t) decltype(a_)::value * A.N + j + 1] = __builtin_nan(""); });
+      static_for<0, NY>([&](auto a_) { A.y_arrive[(int64_t) decltype(a_)::value * N + j + 1] = __builtin_nan(""); });
       A.accepted[j + 1] = A.rejected[j + 1] = 0;
       continue;
     }
-    if (j >= A.sec_s[k + 1] && k < A.K - 1) ++k;
-    const int sk = A.sec_s[k], n = A.sec_s[k + 1] - sk + 1;
+    if (j >= sec_s[k + 1] && k < A.v.K - 1) ++k;
+    const int sk = sec_s[k], n = sec_s[k + 1] - sk + 1;
     const int64_t off = (int64_t)sk + k;
-    const double ta = A.sec_tau[k], w = A.sec_tau[k + 1] - ta;
+    const double ta = A.c.sec_tau[k], w = A.c.sec_tau[k + 1] - ta;
     const double ca = 2.0 * (A.tau[j] - ta) / w - 1.0, cb = 2.0 * (A.tau[j + 1] - ta) / w - 1.0;
     const double g = stretch * (0.5 * w);
     int n_acc = 0, n_rej = 0;
@@ -577,15 +592,127 @@ __device__ __forceinline__ void sol_propagate(const PcSolPropagateArgs& A) {
     A.rejected[j + 1] = n_rej;
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
-      A.y_arrive[(int64_t)a * A.N + j + 1] = status >= 0 ? __builtin_nan("") : y[a];
+      A.y_arrive[(int64_t)a * N + j + 1] = status >= 0 ? __builtin_nan("") : y[a];
     });
   }
   A.seg_status[i] = status;
 }
 
+// ---------------------------------------------------------------------------------------------
+// ph mesh-error estimate (pycollo/mesh_refinement.py:63-240 + solution/solution_abc.py:60-107)
+// pc_mesh_err_p<i>: one workgroup per run of sections; section k owns n_k + 1 consecutive lanes = its nodes on the
+// "ph mesh" (one node more per section).  Lane j < n_k also evaluates solution node j of the section.
+//   1. f at the solution nodes                      (casadi_solution.py:71)
+//   2. states / controls at the interior ph nodes from the section's interpolants, as two small
+//      table contractions:  y_ph = y_start + stretch h_k B f,   u_ph = E u   (solution_abc.py:70-100)
+//   3. f at the ph nodes, Y_ph = y_start + stretch h_k A_(n+1) f_ph          (mesh_refinement.py:199-210)
+//   4. |Y_ph - y_ph| relative to 1 + (1 + max|y_ph|) per state, section maximum (mesh_refinement.py:211-233)
+// ---------------------------------------------------------------------------------------------
+// maximum that keeps a NaN from either side, as np.max does (fmax returns the other operand)
+__device__ __forceinline__ double nan_max(double m, double x) { return (x > m || x != x) ? x : m; }
+
+template <class M>
+__device__ __forceinline__ void mesh_error(const PcRefineArgs& A) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NU = St::NU;
+  extern __shared__ double smem[];
+  const int tid = threadIdx.x, TB = blockDim.x;
+  const PcPhaseView& V = A.v;
+  double* s_B = smem;
+  double* s_E = s_B + A.tab_total_BE;
+  double* s_A = s_E + A.tab_total_BE;
+  double* s_fs = s_A + A.tab_total_A;          // [NY][TB] f at solution nodes
+  double* s_ys = s_fs + NY * TB;               // [NY][TB] y at solution nodes
+  double* s_us = s_ys + NY * TB;               // [NU][TB]
+  double* s_yp = s_us + (NU > 0 ? NU : 1) * TB;  // [NY][TB] y on the ph mesh
+  double* s_fp = s_yp + NY * TB;               // [NY][TB] f on the ph mesh
+  double* s_re = s_fp + NY * TB;               // [TB] row maxima of the relative error
+  double* s_ae = s_re + TB;                    // [NY][TB] absolute errors
+  int* s_sec = reinterpret_cast<int*>(s_ae + NY * TB);   // [TB] section of every lane
+  for (int i = tid; i < A.tab_total_BE; i += TB) {
+    s_B[i] = A.tabB[i];
+    s_E[i] = A.tabE[i];
+  }
+  for (int i = tid; i < A.tab_total_A; i += TB) s_A[i] = A.tabA[i];
+  const SolLane L = sol_lane_map(V, A.tile_k0[blockIdx.x], A.tile_k0[blockIdx.x + 1], A.lane0, 1, s_sec);
+  const bool active = L.active;
+  const int k = L.k, n = L.n, j = L.j, l0 = L.l0;
+  double t0, tF;
+  sol_times<M>(V, t0, tF);
+  const double stretch = 0.5 * (tF - t0);
+  double h = 0.0;
+  double v[St::NV > 0 ? St::NV : 1], F[NY > 0 ? NY : 1];
+  if (active) {
+    h = A.sec_h[k];
+    sol_params<M>(V, v);
+    if (j < n) {   // this lane doubles as solution node j of its section
+      sol_node<M>(V, L.sk + j, v);
+      M::eval_f(v, F);
+      static_for<0, NY>([&](auto a_) {
+        constexpr int a = decltype(a_)::value;
+        s_fs[a * TB + tid] = F[a];
+        s_ys[a * TB + tid] = v[a];
+      });
+      static_for<0, NU>([&](auto b_) { s_us[decltype(b_)::value * TB + tid] = v[NY + decltype(b_)::value]; });
+    }
+  }
+  __syncthreads();
+  if (active) {
+    if (j == 0 || j == n) {   // section boundaries keep the solution's values (mesh_refinement.py:164-166,176-178)
+      const int src = l0 + (j == 0 ? 0 : n - 1);
+      static_for<0, NY>([&](auto a_) { v[decltype(a_)::value] = s_ys[decltype(a_)::value * TB + src]; });
+      static_for<0, NU>([&](auto b_) { v[NY + decltype(b_)::value] = s_us[decltype(b_)::value * TB + src]; });
+    } else {
+      const int row = A.offBE[n] + (j - 1) * n;
+      static_for<0, NY>([&](auto a_) {
+        constexpr int a = decltype(a_)::value;
+        v[a] = s_ys[a * TB + l0] + stretch * (h * sol_row_dot(s_B + row, s_fs + a * TB + l0, n));
+      });
+      static_for<0, NU>([&](auto b_) {
+        constexpr int b = decltype(b_)::value;
+        v[NY + b] = sol_row_dot(s_E + row, s_us + b * TB + l0, n);
+      });
+    }
+    M::eval_f(v, F);
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      s_yp[a * TB + tid] = v[a];
+      s_fp[a * TB + tid] = F[a];
+    });
+  }
+  __syncthreads();
+  double rel = 0.0;
+  if (active && j >= 1) {
+    const double* At = s_A + A.offA[n] + (j - 1) * (n + 1);
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      const double Yph = s_yp[a * TB + l0] + stretch * (h * sol_row_dot(At, s_fp + a * TB + l0, n + 1));
+      const double err = fabs(Yph - s_yp[a * TB + tid]);
+      double mx = 0.0;
+      for (int i = 1; i <= n; ++i) mx = nan_max(mx, fabs(s_yp[a * TB + l0 + i]));
+      rel = nan_max(rel, err / (1.0 + (mx + 1.0)));
+      s_ae[a * TB + tid] = err;
+    });
+    s_re[tid] = rel;
+  }
+  __syncthreads();
+  if (active && j == 0) {
+    double m = 0.0;
+    for (int i = 1; i <= n; ++i) m = nan_max(m, s_re[l0 + i]);
+    A.max_rel[k] = m;
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      double ma = 0.0;
+      for (int i = 1; i <= n; ++i) ma = nan_max(ma, s_ae[a * TB + l0 + i]);
+      A.max_abs[(int64_t)k * NY + a] = ma;
+    });
+  }
+}
+
 }  // namespace pc
 
-// the five entry points of phase I, instantiated by the generated source once per phase
+// the five entry points of phase I, instantiated by the generated source once per phase (pc_mesh_err_p<i> is emitted by
+// the generator itself)
 #define PC_SOL_ENTRY_POINTS(I)                                                                               \
   extern "C" __global__ void __launch_bounds__(256) pc_sol_fit_p##I(PcSolFitArgs a) {                        \
     pc::sol_fit<gen::Phase##I>(a);                                                                           \

@@ -3,7 +3,9 @@
 // pc_solution_plan.hpp; the kernels are pc_solution.hpp, compiled into the model's code object.
 //
 // A solution owns a copy of the point it was made from and everything derived from it; it reads the handle's scaling
-// constants once, at creation, and launches on the handle's stream.  The handle's staged point, its callback caches and
+// constants once, at creation (fill_phase_view), and launches on the handle's stream.  The one thing it does not copy is
+// the section-start table: its kernels read the handle's device copy (sec_s, which a handle never changes), so a solution
+// must be destroyed before its handle, as the stream already demands.  The handle's staged point, its callback caches and
 // its outputs are not touched: an evaluation after any of these calls returns what it returned before.
 //
 // Costates (pc_solution_set_multipliers): the index arithmetic is pc_costate_plan.hpp.  The multipliers belong to the
@@ -22,13 +24,14 @@ struct pc_solution {
   bool has_costate = false;
   struct Phase {
     pcs::FitPlan plan;
-    DevBuf<int32_t> sec_s, tile_k0, lane0;
+    DevBuf<int32_t> tile_k0, lane0;
     DevBuf<double> sec_tau, node_tau, node_t, node_y, node_u, node_f, coef_dy, coef_u;
     DevBuf<double> node_p, node_H, coef_p, nu;   // costates: allocated by pc_solution_set_multipliers
     DevBuf<int32_t> prop_seg, prop_sec;          // propagation: the staged segment list and first sections,
     DevBuf<double> prop_atol;                    // and atol
     hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr, fn_propagate = nullptr;
-    PcSolSampleArgs args;   // everything but the queries, the outputs and the flags
+    PcPhaseView view;       // the phase as of creation: what sampling, the costates and propagation unscale with
+    PcSolCurves curves;     // the polynomials the fit kernel made
     int NY = 0, NU = 0, NQ = 0;
   };
   std::vector<std::unique_ptr<Phase>> ph;
@@ -49,7 +52,6 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
   size_t tau_off = 0;
   for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
     auto& P = Q.ph[ip];
-    auto& D = *h->pd[ip];
     auto S = std::make_unique<pc_solution::Phase>();
     S->NY = P.n_y;
     S->NU = P.n_u;
@@ -57,13 +59,13 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     S->plan = pcs::build_fit_plan(P.K, P.n_k.data(), n_orders, orders, P.n_y, P.n_u, 256, h->lds_limit);
     const pcs::FitPlan& F = S->plan;
     if (F.N != P.N) throw std::runtime_error("solution: the plan's node count differs from the handle's");
-    if (D.scal_host.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
+    if (F.sec_s != P.sec_s) throw std::runtime_error("solution: the plan's section starts differ from the handle's");
+    S->view = fill_phase_view(h, (int)ip, s->d_x.p);
     const std::vector<double> edges = pcs::section_edges(F, tau + tau_off);
     S->tile_k0.upload(F.tile_k0);
     S->lane0.upload(F.lane0);
     S->node_tau.upload(std::vector<double>(tau + tau_off, tau + tau_off + P.N));
     tau_off += (size_t)P.N;
-    S->sec_s.upload(F.sec_s);
     S->sec_tau.upload(edges);
     const size_t ny = (size_t)std::max(1, P.n_y), nu = (size_t)std::max(1, P.n_u);
     S->node_t.alloc((size_t)F.N);
@@ -72,16 +74,16 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     S->node_f.alloc(ny * F.N);
     S->coef_dy.alloc(ny * F.NC);
     S->coef_u.alloc(nu * F.NC);
+    S->curves = PcSolCurves{S->sec_tau.p, S->node_y.p, S->coef_dy.p, S->coef_u.p, F.NC, 0};
     hipFunction_t fn_fit = nullptr;
     HIP_OK(find_fn(h, &fn_fit, ("pc_sol_fit_p" + std::to_string(ip)).c_str()));
     HIP_OK(find_fn(h, &S->fn_sample, ("pc_sol_sample_p" + std::to_string(ip)).c_str()));
     PcSolFitArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.x = s->d_x.p;
+    a.v = S->view;
     a.tau = S->node_tau.p;
     a.tile_k0 = S->tile_k0.p;
     a.lane0 = S->lane0.p;
-    a.sec_s = S->sec_s.p;
     a.tabD = d_D.p;
     a.tabU = s->d_U.p;
     a.node_t = S->node_t.p;
@@ -90,36 +92,11 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     a.node_f = S->node_f.p;
     a.coef_dy = S->coef_dy.p;
     a.coef_u = S->coef_u.p;
-    a.x_off = P.x_off;
-    a.s_off = Q.s_off;
-    a.t_fixed[0] = P.t_fixed[0];
-    a.t_fixed[1] = P.t_fixed[1];
-    a.N = F.N;
-    a.K = F.K;
     a.NC = F.NC;
     a.tab_total = F.tab_total;
-    for (int i = 0; i <= PC_MAX_ORDER; ++i) a.offC[i] = F.offC[i];
-    for (size_t i = 0; i < D.scal_host.size(); ++i) a.scal[i] = D.scal_host[i];
-    size_t sz = sizeof(a);
-    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-    HIP_OK(hipModuleLaunchKernel(fn_fit, F.n_tiles(), 1, 1, F.TB, 1, 1, (unsigned)F.lds_bytes, h->stream, nullptr, cfg));
+    std::memcpy(a.offC, F.offC, sizeof(a.offC));
+    launch_block(fn_fit, F.n_tiles(), F.TB, F.lds_bytes, h->stream, a);
     HIP_OK(hipStreamSynchronize(h->stream));   // the tables above are released on return
-    PcSolSampleArgs& q = S->args;
-    std::memset(&q, 0, sizeof(q));
-    q.x = s->d_x.p;
-    q.sec_s = S->sec_s.p;
-    q.sec_tau = S->sec_tau.p;
-    q.node_y = S->node_y.p;
-    q.coef_dy = S->coef_dy.p;
-    q.coef_u = S->coef_u.p;
-    q.x_off = P.x_off;
-    q.s_off = Q.s_off;
-    q.t_fixed[0] = P.t_fixed[0];
-    q.t_fixed[1] = P.t_fixed[1];
-    q.N = F.N;
-    q.K = F.K;
-    q.NC = F.NC;
-    for (size_t i = 0; i < D.scal_host.size(); ++i) q.scal[i] = D.scal_host[i];
     s->ph.push_back(std::move(S));
   }
 }
@@ -128,7 +105,10 @@ void solution_launch_sample(pc_solution* s, int phase, const double* d_t, int64_
                             double* d_u, double* d_f) {
   auto& S = *s->ph[phase];
   if (n_t == 0) return;
-  PcSolSampleArgs a = S.args;
+  PcSolSampleArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.v = S.view;
+  a.c = S.curves;
   a.t = d_t;
   a.Q = n_t;
   a.flags = flags;
@@ -136,9 +116,7 @@ void solution_launch_sample(pc_solution* s, int phase, const double* d_t, int64_
   a.out_dy = S.NY > 0 ? d_dy : nullptr;
   a.out_u = S.NU > 0 ? d_u : nullptr;
   a.out_f = S.NY > 0 ? d_f : nullptr;
-  size_t sz = sizeof(a);
-  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_OK(hipModuleLaunchKernel(S.fn_sample, (unsigned)pcs::sample_blocks(n_t, 256), 1, 1, 256, 1, 1, 0, s->h->stream, nullptr, cfg));
+  launch_block(S.fn_sample, (unsigned)pcs::sample_blocks(n_t, 256), 256, 0, s->h->stream, a);
 }
 
 // the costates of every phase from the device vector d_lam (pc_sol_costate_p<i>), then the arguments of the sampling calls
@@ -169,11 +147,14 @@ void solution_costate(pc_solution* s, const double* d_lam, int n_orders, const i
     HIP_OK(find_fn(h, &S.fn_sample_costate, ("pc_sol_sample_costate_p" + std::to_string(ip)).c_str()));
     PcSolCostateArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.x = s->d_x.p;
+    // the variables are unscaled as the solution's node values were (the view of creation); the rows are scaled as of
+    // now: the multipliers belong to the constraint scaling the handle holds when they are set (scal's tail: Wd Wp Wi)
+    a.v = S.view;
+    const size_t o_w = D.scal_host.size() - (size_t)(P.n_y + P.n_p + P.n_q);
+    for (size_t i = o_w; i < D.scal_host.size(); ++i) a.v.scal[i] = D.scal_host[i];
     a.lam = d_lam;
     a.tile_k0 = S.tile_k0.p;
     a.lane0 = S.lane0.p;
-    a.sec_s = S.sec_s.p;
     a.sec_tau = S.sec_tau.p;
     a.tabA = d_A.p;
     a.tabU = s->d_U.p;
@@ -181,28 +162,15 @@ void solution_costate(pc_solution* s, const double* d_lam, int n_orders, const i
     a.node_H = S.node_H.p;
     a.coef_p = S.coef_p.p;
     a.nu = S.nu.p;
-    a.x_off = P.x_off;
-    a.s_off = Q.s_off;
     a.c_off = P.c_off;
     a.c_int_off = P.c_int_off;
     a.wJ = h->w_J;
-    a.N = F.N;
-    a.K = F.K;
     a.NC = F.NC;
     a.tab_total = F.tab_total;
     a.a_total = a_total;
-    for (int i = 0; i <= PC_MAX_ORDER; ++i) {
-      a.offC[i] = F.offC[i];
-      a.offA[i] = C.offA[i];
-    }
-    // the variables are unscaled as the solution's node values were; the row scaling is the handle's of now
-    constexpr size_t n_scal = sizeof(a.scal) / sizeof(a.scal[0]);
-    for (size_t i = 0; i < n_scal; ++i) a.scal[i] = S.args.scal[i];
-    const size_t o_w = D.scal_host.size() - (size_t)(P.n_y + P.n_p + P.n_q);
-    for (size_t i = o_w; i < D.scal_host.size(); ++i) a.scal[i] = D.scal_host[i];
-    size_t sz = sizeof(a);
-    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-    HIP_OK(hipModuleLaunchKernel(fn, F.n_tiles(), 1, 1, F.TB, 1, 1, (unsigned)C.lds_bytes, h->stream, nullptr, cfg));
+    std::memcpy(a.offC, F.offC, sizeof(a.offC));
+    std::memcpy(a.offA, C.offA, sizeof(a.offA));
+    launch_block(fn, F.n_tiles(), F.TB, C.lds_bytes, h->stream, a);
   }
   HIP_OK(hipStreamSynchronize(h->stream));   // d_A is released on return; a caller's device vector is free again
   s->has_costate = true;
@@ -230,7 +198,8 @@ void solution_launch_sample_costate(pc_solution* s, int phase, const double* d_t
   if (n_t == 0) return;
   PcSolCostateSampleArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.s = S.args;
+  a.s.v = S.view;
+  a.s.c = S.curves;
   a.s.t = d_t;
   a.s.Q = n_t;
   a.s.flags = flags;
@@ -238,10 +207,7 @@ void solution_launch_sample_costate(pc_solution* s, int phase, const double* d_t
   a.nu = S.nu.p;
   a.out_p = d_p;
   a.out_H = d_H;
-  size_t sz = sizeof(a);
-  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_OK(hipModuleLaunchKernel(S.fn_sample_costate, (unsigned)pcs::sample_blocks(n_t, 256), 1, 1, 256, 1, 1, 0, s->h->stream, nullptr,
-                               cfg));
+  launch_block(S.fn_sample_costate, (unsigned)pcs::sample_blocks(n_t, 256), 256, 0, s->h->stream, a);
 }
 
 int solution_create(pc_handle* h, const double* x, bool x_on_device, int n_orders, const int32_t* orders, const double* tabD,
@@ -282,12 +248,9 @@ void solution_launch_propagate(pc_solution* s, int phase, int64_t n_seg, const i
   S.prop_atol.upload(std::vector<double>(atol, atol + S.NY));
   PcSolPropagateArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.x = S.args.x;
+  a.v = S.view;
+  a.c = S.curves;
   a.tau = S.node_tau.p;
-  a.sec_s = S.sec_s.p;
-  a.sec_tau = S.sec_tau.p;
-  a.node_y = S.node_y.p;
-  a.coef_u = S.coef_u.p;
   a.seg_node = S.prop_seg.p;
   a.seg_sec = S.prop_sec.p;
   a.atol = S.prop_atol.p;
@@ -295,22 +258,11 @@ void solution_launch_propagate(pc_solution* s, int phase, int64_t n_seg, const i
   a.accepted = d_acc;
   a.rejected = d_rej;
   a.seg_status = d_status;
-  a.x_off = S.args.x_off;
-  a.s_off = S.args.s_off;
-  a.t_fixed[0] = S.args.t_fixed[0];
-  a.t_fixed[1] = S.args.t_fixed[1];
   a.rtol = rtol;
-  a.N = S.plan.N;
-  a.K = S.plan.K;
-  a.NC = S.plan.NC;
   a.n_seg = P.n_seg;
   a.substeps = (int32_t)substeps;
   a.max_steps = (int32_t)max_steps;
-  constexpr size_t n_scal = sizeof(a.scal) / sizeof(a.scal[0]);
-  for (size_t i = 0; i < n_scal; ++i) a.scal[i] = S.args.scal[i];
-  size_t sz = sizeof(a);
-  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_OK(hipModuleLaunchKernel(S.fn_propagate, (unsigned)P.blocks, 1, 1, (unsigned)P.TB, 1, 1, 0, s->h->stream, nullptr, cfg));
+  launch_block(S.fn_propagate, (unsigned)P.blocks, (unsigned)P.TB, 0, s->h->stream, a);
 }
 
 pc_solution::Phase& solution_costate_phase(pc_solution* s, int phase) {

@@ -444,6 +444,50 @@ class Solution:
         return pc
 
     # ---- dense output ------------------------------------------------------------------------------
+    def _queries(self, phase, t, tau, extrapolate, *, check_range=True, host_only=False):
+        """``(phase, q, flags)`` of a sampling call: the queries as a contiguous float64 NumPy array or (unless
+        ``host_only``) CUDA tensor.  Raises, in this order: bad ``t`` / ``tau``, phase out of range, with ``check_range``
+        a NaN or a query outside the phase, the solution is closed."""
+        q, is_tau = normalise_query(t, tau)
+        phase = self._phase(phase, need_handle=False)
+        flags = (PC_SOLUTION_TAU if is_tau else 0) | (PC_SOLUTION_EXTRAPOLATE if extrapolate else 0)
+        if _is_torch(q) and not host_only:
+            import torch
+            if q.dtype != torch.float64 or not q.is_cuda:
+                raise ValueError("a tensor of queries must be float64 on the GPU")
+            q, isnan = q.contiguous(), torch.isnan
+        else:
+            q, isnan = np.ascontiguousarray(np.asarray(q, dtype=np.float64)), np.isnan
+        if check_range and q.shape[0]:
+            has_nan = bool(isnan(q).any())
+            lo, hi = (0.0, 0.0) if has_nan else (float(q.min()), float(q.max()))
+            lo, hi, slack = _tau_extremes(lo, hi, is_tau, self.initial_time[phase], self.final_time[phase])
+            check_queries(lo, hi, has_nan, extrapolate, slack)
+        self._phase(phase)     # (the device is needed from here on)
+        return phase, q, flags
+
+    def _sample_into(self, host_call, device_call, phase, q, flags, shapes):
+        """One output array per entry of ``shapes`` (None: not wanted), where the queries live, filled by the exported
+        call: NumPy queries -> ``host_call``, a device tensor -> ``device_call`` on the handle's stream."""
+        Q = int(q.shape[0])
+        if _is_torch(q):
+            import torch
+            outs = [None if sh is None else torch.empty(sh, dtype=torch.float64, device=q.device) for sh in shapes]
+            ptr = lambda a: a.data_ptr() if (a is not None and a.numel()) else None   # noqa: E731
+            torch.cuda.current_stream(q.device).synchronize()     # the handle's stream is not torch's
+            self._check(device_call(self._h, phase, ptr(q), Q, flags, *(ptr(a) for a in outs)))
+            self._check(self._lib.pc_synchronize(self.engine._h))
+        else:
+            outs = [None if sh is None else np.empty(sh) for sh in shapes]
+            ptr = lambda a: a.ctypes.data if (a is not None and a.size) else None   # noqa: E731
+            self._check(host_call(self._h, phase, ptr(q), Q, flags, *(ptr(a) for a in outs)))
+        return outs
+
+    def _sample(self, phase, q, flags, with_f):
+        pl, Q = self.engine.layout.phases[phase], int(q.shape[0])
+        return self._sample_into(self._lib.pc_solution_sample, self._lib.pc_solution_sample_device, phase, q, flags,
+                                 [(pl.n_y, Q), (pl.n_y, Q), (pl.n_u, Q), (pl.n_y, Q) if with_f else None])
+
     def sample(self, phase: int, t=None, *, tau=None, residual: bool = False, extrapolate: bool = False):
         """``(y [n_y][Q], ydot [n_y][Q], u [n_u][Q])`` at the Q times ``t`` (or abscissae ``tau`` in [-1, 1]) of one
         phase, in the order given (any order, duplicates allowed); with ``residual=True`` a fourth array
@@ -451,41 +495,7 @@ class Solution:
         torch device tensor in, torch tensors on that device out.  Queries outside the phase raise ``ValueError``
         unless ``extrapolate=True`` (then the end sections' polynomials are extended); a time within 8 eps (in tau) of
         the phase's end, such as ``node_time``'s own last entry, is the end."""
-        q, is_tau = normalise_query(t, tau)
-        phase = self._phase(phase, need_handle=False)
-        t0, tF = self.initial_time[phase], self.final_time[phase]
-        flags = (PC_SOLUTION_TAU if is_tau else 0) | (PC_SOLUTION_EXTRAPOLATE if extrapolate else 0)
-        Q = int(q.shape[0])
-        if _is_torch(q):
-            import torch
-            if q.dtype != torch.float64 or not q.is_cuda:
-                raise ValueError("a tensor of queries must be float64 on the GPU")
-            q = q.contiguous()
-            if Q:
-                has_nan = bool(torch.isnan(q).any())
-                lo, hi, slack = _tau_extremes(float(q.min()), float(q.max()), is_tau, t0, tF)
-                check_queries(lo, hi, has_nan, extrapolate, slack)
-            self._phase(phase)     # (the device is needed from here on)
-            pl = self.engine.layout.phases[phase]
-            new = lambda rows: torch.empty((rows, Q), dtype=torch.float64, device=q.device)   # noqa: E731
-            y, dy, u = new(pl.n_y), new(pl.n_y), new(pl.n_u)
-            f = new(pl.n_y) if residual else None
-            ptr = lambda a: a.data_ptr() if (a is not None and a.numel()) else None   # noqa: E731
-            torch.cuda.current_stream(q.device).synchronize()     # the handle's stream is not torch's
-            self._check(self._lib.pc_solution_sample_device(self._h, phase, ptr(q), Q, flags, ptr(y), ptr(dy), ptr(u), ptr(f)))
-            self._check(self._lib.pc_synchronize(self.engine._h))
-        else:
-            q = np.ascontiguousarray(q)
-            if Q:
-                has_nan = bool(np.isnan(q).any())
-                lo, hi, slack = _tau_extremes(0.0 if has_nan else float(q.min()), 0.0 if has_nan else float(q.max()), is_tau, t0, tF)
-                check_queries(lo, hi, has_nan, extrapolate, slack)
-            self._phase(phase)     # (the device is needed from here on)
-            pl = self.engine.layout.phases[phase]
-            y, dy, u = np.empty((pl.n_y, Q)), np.empty((pl.n_y, Q)), np.empty((pl.n_u, Q))
-            f = np.empty((pl.n_y, Q)) if residual else None
-            ptr = lambda a: a.ctypes.data if (a is not None and a.size) else None   # noqa: E731
-            self._check(self._lib.pc_solution_sample(self._h, phase, ptr(q), Q, flags, ptr(y), ptr(dy), ptr(u), ptr(f)))
+        y, dy, u, f = self._sample(*self._queries(phase, t, tau, extrapolate), residual)
         if residual:
             return y, dy, u, dy - f
         return y, dy, u
@@ -494,16 +504,7 @@ class Solution:
         """``pc_solution_sample`` as it is (NumPy queries): ``(y, ydot, u, f)`` with f(y(t), u(t), q, t, s) itself as
         the fourth array, and no range check -- a query outside the phase gives NaN in every output unless
         ``extrapolate=True``."""
-        q, is_tau = normalise_query(t, tau)
-        phase = self._phase(phase)
-        pl = self.engine.layout.phases[phase]
-        q = np.ascontiguousarray(np.asarray(q, dtype=np.float64))
-        Q = int(q.shape[0])
-        flags = (PC_SOLUTION_TAU if is_tau else 0) | (PC_SOLUTION_EXTRAPOLATE if extrapolate else 0)
-        y, dy, u, f = np.empty((pl.n_y, Q)), np.empty((pl.n_y, Q)), np.empty((pl.n_u, Q)), np.empty((pl.n_y, Q))
-        ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
-        self._check(self._lib.pc_solution_sample(self._h, phase, ptr(q), Q, flags, ptr(y), ptr(dy), ptr(u), ptr(f)))
-        return y, dy, u, f
+        return tuple(self._sample(*self._queries(phase, t, tau, extrapolate, check_range=False, host_only=True), True))
 
     def sample_costate(self, phase: int, t=None, *, tau=None, extrapolate: bool = False):
         """``(p [n_y][Q], H [Q])`` at the Q times ``t`` (or abscissae ``tau``) of one phase: the costates' section
@@ -511,45 +512,13 @@ class Solution:
         checks and array types as in :meth:`sample`.  ``ValueError`` if the solution was made without multipliers."""
         if self.costate is None:
             raise ValueError("the solution was made without multipliers: it has no costates")
-        q, is_tau = normalise_query(t, tau)
-        phase = self._phase(phase, need_handle=False)
-        t0, tF = self.initial_time[phase], self.final_time[phase]
-        flags = (PC_SOLUTION_TAU if is_tau else 0) | (PC_SOLUTION_EXTRAPOLATE if extrapolate else 0)
-        Q = int(q.shape[0])
-        if _is_torch(q):
-            import torch
-            if q.dtype != torch.float64 or not q.is_cuda:
-                raise ValueError("a tensor of queries must be float64 on the GPU")
-            q = q.contiguous()
-            if Q:
-                has_nan = bool(torch.isnan(q).any())
-                lo, hi, slack = _tau_extremes(float(q.min()), float(q.max()), is_tau, t0, tF)
-                check_queries(lo, hi, has_nan, extrapolate, slack)
-            self._phase(phase)
-            pl = self.engine.layout.phases[phase]
-            p = torch.empty((pl.n_y, Q), dtype=torch.float64, device=q.device)
-            H = torch.empty((Q,), dtype=torch.float64, device=q.device)
-            ptr = lambda a: a.data_ptr() if a.numel() else None   # noqa: E731
-            torch.cuda.current_stream(q.device).synchronize()     # the handle's stream is not torch's
-            self._check(self._lib.pc_solution_sample_costate_device(self._h, phase, ptr(q), Q, flags, ptr(p), ptr(H)))
-            self._check(self._lib.pc_synchronize(self.engine._h))
-        else:
-            q = np.ascontiguousarray(q)
-            if Q:
-                has_nan = bool(np.isnan(q).any())
-                lo, hi, slack = _tau_extremes(0.0 if has_nan else float(q.min()), 0.0 if has_nan else float(q.max()), is_tau, t0, tF)
-                check_queries(lo, hi, has_nan, extrapolate, slack)
-            self._phase(phase)
-            p, H = self.sample_costate_unchecked(phase, q, flags)
-        return p, H
+        return self.sample_costate_unchecked(*self._queries(phase, t, tau, extrapolate))
 
     def sample_costate_unchecked(self, phase, q, flags):
         """``pc_solution_sample_costate`` as it is: no range check, NaN for a query outside the phase."""
-        pl = self.engine.layout.phases[phase]
-        Q = int(q.shape[0])
-        p, H = np.empty((pl.n_y, Q)), np.empty(Q)
-        ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
-        self._check(self._lib.pc_solution_sample_costate(self._h, phase, ptr(q), Q, flags, ptr(p), ptr(H)))
+        pl, Q = self.engine.layout.phases[phase], int(q.shape[0])
+        p, H = self._sample_into(self._lib.pc_solution_sample_costate, self._lib.pc_solution_sample_costate_device, phase, q,
+                                 flags, [(pl.n_y, Q), (Q,)])
         return p, H
 
     # ---- propagation -------------------------------------------------------------------------------
