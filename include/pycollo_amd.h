@@ -339,7 +339,7 @@ const char* pc_kkt_last_error(void);
 int pc_kkt_create(const pc_kkt_desc* desc, const double* d_jac, const double* d_hess, int device, pc_kkt** out);
 void pc_kkt_destroy(pc_kkt* k);
 /* Which of the solver's builds the handle runs (chosen in pc_kkt_create from the block counts and the PYCOLLO_AMD_KKT_*
- * environment, all read there). */
+ * environment, all read there; the rules: csrc/pc_kkt_shape.hpp). */
 typedef struct {
   int64_t n_leaf, n_chain, nb;
   int64_t n_mv_long;               /* rows of the product cut into chunks */
@@ -354,6 +354,11 @@ typedef struct {
   int32_t reserved;
 } pc_kkt_info;
 int pc_kkt_get_info(const pc_kkt* k, pc_kkt_info* info);
+/* Host-only: pc_kkt_info as a fresh handle on `desc` would report it (csrc/pc_kkt_shape.hpp, the shape pc_kkt_create builds
+ * before it touches the device, under the same PYCOLLO_AMD_KKT_* environment), with leaf_forward_stage = what the first
+ * solve will pick; fails where pc_kkt_create would refuse the descriptor.  For the CPU tests, which stand on either side
+ * of every size threshold without a device. */
+int pc_kkt_shape_info(const pc_kkt_desc* desc, pc_kkt_info* out);
 /* assemble from the current device G~ / H~ (use_hess = 0: W = 0, e.g. least-squares multipliers) and dvec[nu]
  * (host: Sigma + dw on primal unknowns, -dc on multipliers), factorise; returns the pivot signs */
 int pc_kkt_factor(pc_kkt* k, int use_hess, const double* dvec, int32_t* n_pos, int32_t* n_neg);

@@ -490,7 +490,7 @@ extern "C" {
 
 int pc_deriv_plan(const pc_handle* h, int32_t* n_colours, int32_t* colour, uint8_t* jac_flag, uint8_t* hess_flag,
                   uint8_t* jgrad_flag) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h) throw std::runtime_error("null handle");
     const pcd::Plan& P = deriv_plan_of(h);
     if (n_colours) *n_colours = P.n_colours;
@@ -504,7 +504,7 @@ int pc_deriv_plan(const pc_handle* h, int32_t* n_colours, int32_t* colour, uint8
 int pc_check_derivatives_device(pc_handle* h, const double* d_x, double obj_factor, const double* d_lambda,
                                 const double* d_jac_override, const double* d_hess_override, const pc_deriv_opts* opts,
                                 pc_deriv_report* report, void* stream) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     if (!d_x || !report) throw std::runtime_error("null x or report");
     for (size_t ip = 0; ip < h->pd.size(); ++ip) {

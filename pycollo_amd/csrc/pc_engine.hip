@@ -15,6 +15,7 @@
 
 #include "../../include/pycollo_amd.h"
 #include "pc_args.h"
+#include "pc_host.hpp"
 #include "pc_pattern.hpp"
 #include "pc_desc.hpp"
 #include "pc_deriv.hpp"
@@ -29,55 +30,10 @@ thread_local std::string g_err;
 
 void set_err(const std::string& s) { g_err = s; }
 
-#define HIP_OK(expr)                                                                             \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess)                                                                        \
-      throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-
 using pcp::phase_nfs;
 using pcp::phase_lds_bytes;
 using pcp::phase_lds_out;
 using pcp::phase_max_tile_rows;
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  void alloc(size_t count) {
-    free();
-    n = count;
-    if (count) HIP_OK(hipMalloc(&p, count * sizeof(T)));
-  }
-  void upload(const std::vector<T>& v) {
-    if (v.size() != n) alloc(v.size());   // same size: keep the allocation (pointers held in argument blocks stay valid)
-    if (!v.empty()) HIP_OK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  }
-  void free() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  ~DevBuf() { free(); }
-};
-
-template <class T>
-struct PinBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  void alloc(size_t count) {
-    free();
-    n = count;
-    if (count) HIP_OK(hipHostMalloc(&p, count * sizeof(T), hipHostMallocDefault));
-  }
-  void free() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  ~PinBuf() { free(); }
-};
 
 struct PhaseDev {
   DevBuf<int32_t> tile_k0, tile_n0, sec_s;
@@ -655,17 +611,6 @@ hipError_t find_fn(pc_handle* h, hipFunction_t* fn, const char* name) {
   return e;
 }
 
-template <class F>
-int guarded(F&& f) {
-  try {
-    f();
-    return 1;
-  } catch (const std::exception& e) {
-    set_err(e.what());
-    return 0;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -675,7 +620,7 @@ const char* pc_last_error(void) { return g_err.c_str(); }
 int pc_create(const pc_problem_desc* d, pc_handle** out) {
   if (out) *out = nullptr;
   std::unique_ptr<pc_handle> h;
-  const int ok = guarded([&] {
+  const int ok = guarded(g_err, [&] {
     if (!d || !out) throw std::runtime_error("null descriptor or output pointer");
     if (d->n_phases < 1 || d->n_phases > PC_MAX_PHASES) throw std::runtime_error("n_phases must be in [1, 8]");
     h.reset(new pc_handle());
@@ -1205,7 +1150,7 @@ void pc_destroy(pc_handle* h) {
 }
 
 int pc_get_info(const pc_handle* h, pc_info* info) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h || !info) throw std::runtime_error("null argument");
     const auto& Q = h->Q;
     info->n = (int32_t)Q.num_x;
@@ -1227,7 +1172,7 @@ int pc_get_info(const pc_handle* h, pc_info* info) {
 }
 
 int pc_sizes(const pc_handle* h, int32_t* n, int32_t* m, int64_t* nnz_jac, int64_t* nnz_hess) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h) throw std::runtime_error("null handle");
     if (n) *n = (int32_t)h->Q.num_x;
     if (m) *m = (int32_t)h->Q.num_c;
@@ -1237,7 +1182,7 @@ int pc_sizes(const pc_handle* h, int32_t* n, int32_t* m, int64_t* nnz_jac, int64
 }
 
 int pc_jac_structure(const pc_handle* h, int32_t* iRow, int32_t* jCol) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h || !iRow || !jCol) throw std::runtime_error("null argument");
     std::memcpy(iRow, h->Q.g_row.data(), h->Q.g_row.size() * sizeof(int32_t));
     std::memcpy(jCol, h->Q.g_col.data(), h->Q.g_col.size() * sizeof(int32_t));
@@ -1245,7 +1190,7 @@ int pc_jac_structure(const pc_handle* h, int32_t* iRow, int32_t* jCol) {
 }
 
 int pc_hess_structure(const pc_handle* h, int32_t* iRow, int32_t* jCol) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h || !iRow || !jCol) throw std::runtime_error("null argument");
     std::memcpy(iRow, h->Q.h_row.data(), h->Q.h_row.size() * sizeof(int32_t));
     std::memcpy(jCol, h->Q.h_col.data(), h->Q.h_col.size() * sizeof(int32_t));
@@ -1253,7 +1198,7 @@ int pc_hess_structure(const pc_handle* h, int32_t* iRow, int32_t* jCol) {
 }
 
 int pc_set_scaling(pc_handle* h, const double* V, const double* r, const double* W, double w_J) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h || !V || !r || !W) throw std::runtime_error("null argument");
     if (h->device >= 0) {
       // evaluations may be in flight on a caller's stream (pc_eval_all_device): none may still read the tables
@@ -1273,7 +1218,7 @@ int pc_set_scaling(pc_handle* h, const double* V, const double* r, const double*
 
 int pc_eval_all_device(pc_handle* h, const double* d_x, double obj_factor, const double* d_lambda, double* d_g,
                        double* d_jac, double* d_hess, void* stream) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     check_timeout(h);   // a previous device-API evaluation whose tail gave up: say so before queueing more work
@@ -1284,7 +1229,7 @@ int pc_eval_all_device(pc_handle* h, const double* d_x, double obj_factor, const
 }
 
 int pc_check(pc_handle* h) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     check_timeout(h);
   });
@@ -1292,7 +1237,7 @@ int pc_check(pc_handle* h) {
 
 int pc_launch_bulk_device(pc_handle* h, const double* d_x, const double* d_lambda, double* d_g, double* d_jac,
                           double* d_hess, void* stream) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -1303,7 +1248,7 @@ int pc_launch_bulk_device(pc_handle* h, const double* d_x, const double* d_lambd
 
 int pc_launch_bulk_flags_device(pc_handle* h, const double* d_x, const double* d_lambda, double* d_g, double* d_jac,
                                 double* d_hess, int flags, void* stream) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     if (flags & ~(PC_FLAG_C | PC_FLAG_G | PC_FLAG_H)) throw std::runtime_error("flags must be a combination of 1 (g), 2 (jac_g), 4 (hess)");
@@ -1314,7 +1259,7 @@ int pc_launch_bulk_flags_device(pc_handle* h, const double* d_x, const double* d
 
 int pc_launch_tail_device(pc_handle* h, const double* d_x, double obj_factor, const double* d_lambda, double* d_g,
                           double* d_jac, double* d_hess, void* stream) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -1328,7 +1273,7 @@ int pc_launch_tail_device(pc_handle* h, const double* d_x, double obj_factor, co
 // Synchronises `stream`.
 int pc_launch_tail_objective_device(pc_handle* h, const double* d_x, double obj_factor, const double* d_lambda, double* d_g,
                                     double* d_jac, double* d_hess, void* stream, double* f, double* grad) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     auto& Q = h->Q;
     h->fc_valid = h->small_synced = h->G_synced = false;
@@ -1346,7 +1291,7 @@ int pc_launch_tail_objective_device(pc_handle* h, const double* d_x, double obj_
 }
 
 int pc_set_tile_range(pc_handle* h, int phase, int tile_begin, int tile_end) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h || phase < 0 || phase >= (int)h->pd.size()) throw std::runtime_error("phase out of range");
     auto& D = *h->pd[phase];
     if (tile_begin < 0 || tile_end < tile_begin || tile_end > D.n_tiles) throw std::runtime_error("tile range out of range");
@@ -1363,7 +1308,7 @@ int pc_set_tile_range(pc_handle* h, int phase, int tile_begin, int tile_end) {
 }
 
 int pc_phase_tiles(const pc_handle* h, int phase, int32_t* n_tiles, int32_t* nred, int32_t* tile_k0) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h || phase < 0 || phase >= (int)h->pd.size()) throw std::runtime_error("phase out of range");
     const auto& P = h->Q.ph[phase];
     if (n_tiles) *n_tiles = (int32_t)P.tile_k0.size() - 1;
@@ -1373,7 +1318,7 @@ int pc_phase_tiles(const pc_handle* h, int phase, int32_t* n_tiles, int32_t* nre
 }
 
 int pc_phase_tile_orders(const pc_handle* h, int phase, int32_t* tile_order) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h || phase < 0 || phase >= (int)h->Q.ph.size() || !tile_order) throw std::runtime_error("phase out of range or null output");
     auto& P = h->Q.ph[phase];
     for (size_t t = 0; t + 1 < P.tile_k0.size(); ++t) tile_order[t] = t < P.tile_order.size() ? P.tile_order[t] : 0;
@@ -1381,7 +1326,7 @@ int pc_phase_tile_orders(const pc_handle* h, int phase, int32_t* tile_order) {
 }
 
 int pc_set_partials_buffer(pc_handle* h, int phase, double* d_partials) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!h || phase < 0 || phase >= (int)h->pd.size()) throw std::runtime_error("phase out of range");
     if (h->device >= 0) {
       HIP_OK(hipSetDevice(h->device));
@@ -1395,7 +1340,7 @@ int pc_set_partials_buffer(pc_handle* h, int phase, double* d_partials) {
 
 int pc_eval_all(pc_handle* h, const double* x, double obj_factor, const double* lambda, double* g, double* jac,
                 double* hess) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     auto& Q = h->Q;
     if (!x || !lambda || !g || !jac || !hess) throw std::runtime_error("null argument");
@@ -1417,7 +1362,7 @@ int pc_eval_all(pc_handle* h, const double* x, double obj_factor, const double* 
 }
 
 int pc_host_buffers(pc_handle* h, double** x, double** lambda, double** g, double** jac, double** hess) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     if (x) *x = h->h_in.p;
     if (lambda) *lambda = h->h_in.p + h->o_lam;
@@ -1428,14 +1373,14 @@ int pc_host_buffers(pc_handle* h, double** x, double** lambda, double** g, doubl
 }
 
 int pc_set_prefetch_jac(pc_handle* h, int on) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     h->prefetch_jac = on != 0;
   });
 }
 
 int pc_set_host_mode(pc_handle* h, int mode) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     if (mode < 0 || mode > 3) throw std::runtime_error("host mode must be 0..3");
     HIP_OK(hipStreamSynchronize(h->stream));
@@ -1493,7 +1438,7 @@ static void wait_G(pc_handle* h) {
 }
 
 int pc_eval_f(pc_handle* h, const double* x, int new_x, double* f) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     ensure_fcG(h, x, new_x);
     wait_small(h);
     *f = h->h_out.p[h->o_f];
@@ -1501,7 +1446,7 @@ int pc_eval_f(pc_handle* h, const double* x, int new_x, double* f) {
 }
 
 int pc_eval_grad_f(pc_handle* h, const double* x, int new_x, double* grad) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     ensure_fcG(h, x, new_x);
     wait_small(h);
     auto& Q = h->Q;
@@ -1511,7 +1456,7 @@ int pc_eval_grad_f(pc_handle* h, const double* x, int new_x, double* grad) {
 }
 
 int pc_eval_g(pc_handle* h, const double* x, int new_x, double* g) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     ensure_fcG(h, x, new_x);
     wait_small(h);
     if (g != h->h_out.p + h->o_c) std::memcpy(g, h->h_out.p + h->o_c, h->Q.num_c * sizeof(double));
@@ -1519,7 +1464,7 @@ int pc_eval_g(pc_handle* h, const double* x, int new_x, double* g) {
 }
 
 int pc_eval_jac_g(pc_handle* h, const double* x, int new_x, double* values) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     ensure_fcG(h, x, new_x);
     wait_G(h);
     if (values != h->h_out.p + h->o_G) std::memcpy(values, h->h_out.p + h->o_G, h->Q.g_row.size() * sizeof(double));
@@ -1529,7 +1474,7 @@ int pc_eval_jac_g(pc_handle* h, const double* x, int new_x, double* values) {
 int pc_eval_h(pc_handle* h, const double* x, int new_x, double obj_factor, const double* lambda, int new_lambda,
               double* values) {
   (void)new_lambda;   // sigma and lambda are cheap to restage; H~ is always re-evaluated
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     auto& Q = h->Q;
     stage_x(h, x, new_x);
@@ -1548,7 +1493,7 @@ int pc_eval_h(pc_handle* h, const double* x, int new_x, double obj_factor, const
 
 int pc_eval_resident(pc_handle* h, const double* x, double obj_factor, const double* lambda, double* f, double* grad,
                      double* g) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     auto& Q = h->Q;
     if (!x) throw std::runtime_error("null x");
@@ -1579,7 +1524,7 @@ int pc_eval_resident(pc_handle* h, const double* x, double obj_factor, const dou
 }
 
 int pc_device_results(pc_handle* h, const double** d_g, const double** d_jac, const double** d_hess) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     if (d_g) *d_g = h->d_out.p + h->o_c;
     if (d_jac) *d_jac = h->d_out.p + h->o_G;
@@ -1634,7 +1579,7 @@ int pc_ipopt_eval_h(int n, double* x, int new_x, double obj_factor, int m, doubl
 }
 
 int pc_row_norms_jac(pc_handle* h, const double* x, double* norms) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     // always through the device mirror: the row reduction reads G~ back
     const int mode = h->host_mode;
@@ -1664,7 +1609,7 @@ int pc_row_norms_jac(pc_handle* h, const double* x, double* norms) {
 
 int pc_interp_linear(int device, const double* tau_prev, int n_prev, const double* vals_prev, int n_vars,
                      const double* tau_new, int n_new, double* out) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (n_prev < 2 || n_new < 1 || n_vars < 0) throw std::runtime_error("interpolation needs at least two abscissae");
     int ndev = 0;
     if (device < 0 || hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device)
@@ -1683,7 +1628,7 @@ int pc_interp_linear(int device, const double* tau_prev, int n_prev, const doubl
 }
 
 int pc_copy_runs(const double* d_src, double* d_dst, const int64_t* d_chunks, int64_t n_chunks, void* stream) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (n_chunks <= 0) return;
     if (!d_src || !d_dst || !d_chunks) throw std::runtime_error("null argument");
     hipLaunchKernelGGL(copy_runs_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, d_src, d_dst, d_chunks);
@@ -1695,7 +1640,7 @@ int pc_run_chunk(void) { return PC_RUN_CHUNK; }
 
 int pc_mesh_error(pc_handle* h, int phase, const double* x, int n_orders, const int32_t* orders, const double* tabB,
                   const double* tabE, const double* tabA, double* max_rel, double* max_abs) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     if (phase < 0 || phase >= (int)h->pd.size()) throw std::runtime_error("phase out of range");
     auto& Q = h->Q;
@@ -1742,7 +1687,7 @@ int pc_mesh_error(pc_handle* h, int phase, const double* x, int n_orders, const 
 }
 
 int pc_synchronize(pc_handle* h) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     HIP_OK(hipStreamSynchronize(h->stream));
     check_timeout(h);
@@ -1752,7 +1697,7 @@ int pc_synchronize(pc_handle* h) {
 void* pc_stream(pc_handle* h) { return h ? (void*)h->stream : nullptr; }
 
 int pc_read_symbol(pc_handle* h, const char* name, void* dst, size_t bytes) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     if (!name || !dst) throw std::runtime_error("null symbol name or destination");
     hipDeviceptr_t p = nullptr;

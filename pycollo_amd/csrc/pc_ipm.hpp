@@ -308,7 +308,7 @@ extern "C" {
 int pc_ipm_create(pc_handle* h, pc_kkt* k, const pc_ipm_desc* d, pc_ipm** out) {
   if (out) *out = nullptr;
   std::unique_ptr<pc_ipm> s;
-  const int ok = guarded([&] {
+  const int ok = guarded(g_err, [&] {
     require_device(h);
     if (!k || !d || !out) throw std::runtime_error("null argument");
     if (d->n != h->Q.num_x || d->m != h->Q.num_c) throw std::runtime_error("pc_ipm_create: sizes differ from the NLP's");
@@ -362,7 +362,7 @@ void pc_ipm_destroy(pc_ipm* s) {
 }
 
 int pc_ipm_set_state(pc_ipm* s, const double* v, const double* lam, const double* zl, const double* zu) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s || !v || !lam || !zl || !zu) throw std::runtime_error("null argument");
     require_device(s->h);
     HIP_OK(hipStreamSynchronize(s->h->stream));
@@ -374,7 +374,7 @@ int pc_ipm_set_state(pc_ipm* s, const double* v, const double* lam, const double
 }
 
 int pc_ipm_get_state(pc_ipm* s, double* v, double* lam, double* zl, double* zu, double* c, double* g) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s) throw std::runtime_error("null argument");
     require_device(s->h);
     HIP_OK(hipStreamSynchronize(s->h->stream));
@@ -390,7 +390,7 @@ int pc_ipm_get_state(pc_ipm* s, double* v, double* lam, double* zl, double* zu, 
 // the step and what it was solved from, read only (tests): the solution of the last linear solve [dv ; dlam], the bound
 // multipliers' steps, the right-hand side, the last trial point and the unshifted diagonal the solve was refined against
 int pc_ipm_get_step(pc_ipm* s, double* sol, double* dzl, double* dzu, double* rhs, double* vt, double* dvec_true) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s) throw std::runtime_error("null argument");
     require_device(s->h);
     HIP_OK(hipStreamSynchronize(s->h->stream));
@@ -405,7 +405,7 @@ int pc_ipm_get_step(pc_ipm* s, double* sol, double* dzl, double* dzu, double* rh
 
 // f (scaled by obj_scale), theta = sum |c|, max |c| at the current point; J, grad J, c~ and G~ are evaluated there
 int pc_ipm_eval_point(pc_ipm* s, double* out3) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s || !out3) throw std::runtime_error("null argument");
     require_device(s->h);
     ipm_eval_point(s, s->v.p, s->c.p, true);
@@ -421,7 +421,7 @@ int pc_ipm_eval_point(pc_ipm* s, double* out3) {
 
 // the ten scalars of ipm_errors_kernel at the current point (J^T lambda through the KKT product, as ipm.py::_JT)
 int pc_ipm_errors(pc_ipm* s, double* out10) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s || !out10) throw std::runtime_error("null argument");
     require_device(s->h);
     hipStream_t st = s->h->stream;
@@ -441,7 +441,7 @@ int pc_ipm_errors(pc_ipm* s, double* out10) {
 // out8: 0 dw   1 a_max   2 a_z   3 grad phi . dv   4 phi_mu(v) - f (= mu x barrier sum)   5 factorisations   6 back-substitutions   7 non-finite
 // Returns 1 with out8[0] < 0 when the regularisation failed (the caller ends the solve as ipm.py does).
 int pc_ipm_newton(pc_ipm* s, double mu, double tau, double dw_last, double* out8) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s || !out8) throw std::runtime_error("null argument");
     pc_handle* h = s->h;
     require_device(h);
@@ -490,7 +490,7 @@ int pc_ipm_newton(pc_ipm* s, double mu, double tau, double dw_last, double* out8
 
 // trial point v + alpha dv: f (scaled), theta, mu x barrier sum there
 int pc_ipm_trial(pc_ipm* s, double alpha, double mu, double* out3) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s || !out3) throw std::runtime_error("null argument");
     require_device(s->h);
     hipStream_t st = s->h->stream;
@@ -512,7 +512,7 @@ int pc_ipm_trial(pc_ipm* s, double alpha, double mu, double* out3) {
 // previous corrected trial; the corrected step replaces the Newton step (kept aside: pc_ipm_soc_restore), the bound
 // multipliers' step and the limits follow it.  out8 as pc_ipm_newton's (0: unused).
 int pc_ipm_soc(pc_ipm* s, double alpha, int first, double mu, double tau, double* out8) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s || !out8) throw std::runtime_error("null argument");
     require_device(s->h);
     hipStream_t st = s->h->stream;
@@ -532,7 +532,7 @@ int pc_ipm_soc(pc_ipm* s, double alpha, int first, double mu, double tau, double
 
 // the corrections were rejected: the Newton step, its right-hand side and its bound-multiplier steps back in place
 int pc_ipm_soc_restore(pc_ipm* s, double mu, double tau) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s) throw std::runtime_error("null argument");
     require_device(s->h);
     hipStream_t st = s->h->stream;
@@ -547,7 +547,7 @@ int pc_ipm_soc_restore(pc_ipm* s, double mu, double tau) {
 
 // accept the last trial point: v, lambda, z updated; grad J and G~ evaluated at the new point (c~ is the trial's)
 int pc_ipm_accept(pc_ipm* s, double alpha, double a_z, double mu) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s) throw std::runtime_error("null argument");
     require_device(s->h);
     hipStream_t st = s->h->stream;

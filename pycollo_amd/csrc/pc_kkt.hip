@@ -24,55 +24,16 @@
 #include <vector>
 
 #include "../../include/pycollo_amd.h"
-#include "pc_kkt_cr.hpp"
+#include "pc_host.hpp"
+#include "pc_kkt_shape.hpp"
 
 namespace {
 
 thread_local std::string k_err;
 
-#define KHIP(expr)                                                                               \
-  do {                                                                                           \
-    hipError_t e_ = (expr);                                                                      \
-    if (e_ != hipSuccess)                                                                        \
-      throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(e_));              \
-  } while (0)
-
-template <class T>
-struct Dev {
-  T* p = nullptr;
-  size_t n = 0;
-  void alloc(size_t count) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = count;
-    if (count) KHIP(hipMalloc(&p, count * sizeof(T)));
-  }
-  void upload(const T* src, size_t count) {
-    alloc(count);
-    if (count) KHIP(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-  }
-  ~Dev() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-// pinned host staging: the vectors of a call cross the bus from / to page-locked memory (a pageable hipMemcpyAsync is
-// staged by the runtime through its own bounce buffer, synchronously: ~0.1 ms per 240 KB vector at config 2, more than
-// the solve's kernels)
-template <class T>
-struct Pin {
-  T* p = nullptr;
-  size_t n = 0;
-  void alloc(size_t count) {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    n = count;
-    if (count) KHIP(hipHostMalloc(&p, count * sizeof(T), hipHostMallocDefault));
-  }
-  ~Pin() {
-    if (p) (void)hipHostFree(p);
-  }
-};
+using pck::CrTop;
+using pck::MV_CHUNK;
+using pck::MV_LONG;
 
 enum { SRC_G = 0, SRC_H = 1, SRC_ONE = 2 };
 
@@ -109,7 +70,7 @@ __global__ void kkt_diag(double* __restrict__ vals, const int64_t* __restrict__ 
 // (kind << 30 | index), and the 8 partial sums meet through DPP row shifts.  Rows longer than MV_LONG entries -- the
 // integral / parameter rows with one entry per node -- would serialise 8 lanes over thousands of entries: the host
 // lists them, they are skipped here and done by one workgroup each (kkt_matvec_long).
-constexpr int MV_LANES = 8, MV_LONG = 256;
+constexpr int MV_LANES = 8;
 __device__ __forceinline__ double mv_entry(unsigned src, double coef, const double* __restrict__ G, const double* __restrict__ H, int use_H) {
   const unsigned k = src >> 30, idx = src & 0x3fffffffu;
   const double v = k == SRC_G ? G[idx] : (k == SRC_H ? (use_H ? H[idx] : 0.0) : 1.0);
@@ -142,7 +103,6 @@ __global__ void __launch_bounds__(256) kkt_matvec(const int64_t* __restrict__ pt
 // A long row is cut into chunks of MV_CHUNK entries, one workgroup per chunk (a single workgroup per row walked
 // 10 k entries in 40 dependent rounds of four loads each: 55 us); the chunks' sums are added in chunk order by
 // kkt_matvec_long_finish, so the result does not depend on the launch geometry.
-constexpr int MV_CHUNK = 1024;
 __global__ void __launch_bounds__(256) kkt_matvec_long(const int64_t* __restrict__ chunk_e0, const int64_t* __restrict__ chunk_e1,
                                 const int32_t* __restrict__ col, const uint32_t* __restrict__ src, const double* __restrict__ coef,
                                 const double* __restrict__ G, const double* __restrict__ H, int use_H,
@@ -638,11 +598,6 @@ __global__ void __launch_bounds__(64) kkt_cr_backward(KArgs k, int64_t first) {
 // node, the level's nodes dealt over the waves, a workgroup barrier between levels (what a level leaves in device memory
 // is read by other waves of the same workgroup on the same compute unit).  Same per-node code, same bits.
 // KIND 0: factorisation, 1: forward elimination, 2: back-substitution (levels walked downwards).
-struct CrTop {
-  int64_t ptr[18];     // level offsets into cr_nodes: levels [0, n) of the fused range
-  int32_t n;
-  int32_t wave_bytes;  // LDS per wave: the level kernels' dynamic size + the pull tables
-};
 template <int KIND>
 __global__ void __launch_bounds__(1024) kkt_cr_top(KArgs k, CrTop t) {
   extern __shared__ double lds[];
@@ -926,17 +881,6 @@ __global__ void kkt_leaf_backward(KArgs a) {
   }
 }
 
-template <class F>
-int guarded(F&& f) {
-  try {
-    f();
-    return 1;
-  } catch (const std::exception& e) {
-    k_err = e.what();
-    return 0;
-  }
-}
-
 }  // namespace
 
 struct pc_kkt {
@@ -947,49 +891,51 @@ struct pc_kkt {
   const double* d_H = nullptr;
   int64_t nu = 0, n_dst = 0, total = 0;
   int n_leaf = 0, n_chain = 0, n_phase = 0, nb = 0;
-  int lds_leaf = 0, lds_chain = 0, lds_border = 0;
-  int lds_chain_factor = 0;
-  bool chain_cr = false;     // the chain by cyclic reduction: one launch per level
-  std::vector<int64_t> cr_lvl_ptr;   // nodes of level l: cr_nodes[cr_lvl_ptr[l-1] .. cr_lvl_ptr[l])
-  size_t cr_top_from = 0;            // levels [cr_top_from, cr_lvl_ptr.size()) run in one launch (kkt_cr_top); = size(): none
-  int cr_top_waves = 0, cr_top_lds = 0;
-  CrTop cr_top{};
-  int lds_cr = 0;
-  Dev<double> crbuf;
-  Dev<int64_t> cr_a, cr_b, crP_off, crS_off, crG_off, cr_nodes, cr_mid_a, cr_mid_b, pull_ptr;
-  Dev<int32_t> pull_e;
-  Dev<uint8_t> chain_first, chain_export;
-  bool any_export = false;
-  std::vector<int64_t> export_nodes;    // chain nodes that are not eliminated (a rank's shared nodes), ascending
-  std::vector<int64_t> h_crP_off, h_chain_ptr, h_cr_b;      // host copies for the export calls
-  Dev<double> border_part;   // [border_blocks][nb * nb] partial sums of the border terms (wide borders only)
-  int border_blocks = 0;
-  int lds_leaf_full = 0;   // LDS of the leaf factorisation: the largest leaf block that fits, plus its staging vectors
-  Dev<double> vals, r, leafG, chainG, dvec, vin, vout, src_coef, mv_coef;
-  Dev<int64_t> perm, leaf_ptr, chain_ptr, chain_phase_ptr, leaf_left, leafA_off, leafS_off, chainD_off, chainS_off,
+  pck::Shape s;              // which build of every kernel runs, with how much LDS (pc_kkt_shape.hpp)
+  std::vector<int64_t> h_chain_ptr;      // host copy for the export calls
+  DevBuf<double> crbuf;
+  DevBuf<int64_t> cr_a, cr_b, crP_off, crS_off, crG_off, cr_nodes, cr_mid_a, cr_mid_b, pull_ptr;
+  DevBuf<int32_t> pull_e;
+  DevBuf<uint8_t> chain_first, chain_export;
+  DevBuf<double> border_part;   // [border_blocks][nb * nb] partial sums of the border terms (wide borders only)
+  DevBuf<double> vals, r, leafG, chainG, dvec, vin, vout, src_coef, mv_coef;
+  DevBuf<int64_t> perm, leaf_ptr, chain_ptr, chain_phase_ptr, leaf_left, leafA_off, leafS_off, chainD_off, chainS_off,
       leaf_of_left, leafG_off, chainG_off, dst, run_ptr, diag_pos, mv_ptr;
-  Dev<int32_t> src_kind, src_idx, mv_col;
-  Dev<uint32_t> mv_src;            // kind << 30 | index of every matvec entry
-  Dev<int64_t> mv_long, mv_long_c0, mv_chunk_e0, mv_chunk_e1;   // rows with more than MV_LONG entries, cut into chunks
-  Dev<double> mv_long_part;                                     // one partial sum per chunk
-  int64_t n_mv_long = 0, n_mv_chunks = 0;
-  Dev<double> w_rhs, w_sol, w_res, w_trial, w_dx, w_dvec, w_part, w_norm;   // on-device iterative refinement
-  Pin<double> h_norm;
-  Dev<uint8_t> fixed, chain_last;
-  Dev<int> counts;
-  Pin<int> h_counts;
-  Pin<double> h_a, h_b;      // two vectors in, or one in and one out
+  DevBuf<int32_t> src_kind, src_idx, mv_col;
+  DevBuf<uint32_t> mv_src;            // kind << 30 | index of every matvec entry
+  DevBuf<int64_t> mv_long, mv_long_c0, mv_chunk_e0, mv_chunk_e1;   // rows with more than MV_LONG entries, cut into chunks
+  DevBuf<double> mv_long_part;                                     // one partial sum per chunk
+  DevBuf<double> w_rhs, w_sol, w_res, w_trial, w_dx, w_dvec, w_part, w_norm;   // on-device iterative refinement
+  PinBuf<double> h_norm;
+  DevBuf<uint8_t> fixed, chain_last;
+  DevBuf<int> counts;
+  PinBuf<int> h_counts;
+  PinBuf<double> h_a, h_b;      // two vectors in, or one in and one out
   KArgs args{};
   bool factored = false;
-  // a refined solve stops once ||rhs - K x||_2 <= resid_tol ||rhs||_2 (IPOPT: residual_ratio_max = 1e-10 on its own ratio).
-  // Config 2, per interior-point iteration: no test 1.40 ms and 3.9 back-substitutions, 1e-12 1.03 ms with the objective
-  // unchanged in all ten printed digits, 1e-11 1.06 ms (objective moves in the 8th digit), 1e-9 0.95 ms
-  // (profiles/r04_ipm_iter_time.txt)
-  double resid_tol = 1e-12;
-  int leaf_fwd_env = -1;     // PYCOLLO_AMD_KKT_LEAF_FWD_LDS: kkt_leaf_forward's staging (0 / 1 / 2); -1: by the leaf count
-  int leaf_waves = 4;        // PYCOLLO_AMD_KKT_LEAF_WAVES: waves per leaf of kkt_leaf_factor
   int leaf_forward_stage = -1;   // what the last forward elimination ran (pc_kkt_info)
 };
+
+// the end of a handle, finished or half built: nothing of it may still be queued when its buffers go
+static void release(pc_kkt* k) {
+  if (!k) return;
+  (void)hipSetDevice(k->device);
+  if (k->stream) (void)hipStreamSynchronize(k->stream);
+  if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
+  delete k;
+}
+
+// host vector -> pinned -> device, queued on the handle's stream
+static void stage_up(pc_kkt* k, const double* host, PinBuf<double>& pin, DevBuf<double>& dev) {
+  std::memcpy(pin.p, host, k->nu * sizeof(double));
+  HIP_OK(hipMemcpyAsync(dev.p, pin.p, k->nu * sizeof(double), hipMemcpyHostToDevice, k->stream));
+}
+// device -> pinned -> host vector, once everything queued before it is done
+static void stage_down(pc_kkt* k, const double* dev, PinBuf<double>& pin, double* host) {
+  HIP_OK(hipMemcpyAsync(pin.p, dev, k->nu * sizeof(double), hipMemcpyDeviceToHost, k->stream));
+  HIP_OK(hipStreamSynchronize(k->stream));
+  std::memcpy(host, pin.p, k->nu * sizeof(double));
+}
 
 // Wait for the stream by polling first: a blocking wait costs an interrupt and a wake-up (10-20 us on the MI355X host),
 // and an interior-point iteration makes four or five of them (pivot counts, residual norms)
@@ -998,10 +944,10 @@ static void kwait(hipStream_t st) {
   for (;;) {
     const hipError_t e = hipStreamQuery(st);
     if (e == hipSuccess) return;
-    if (e != hipErrorNotReady) KHIP(e);
+    if (e != hipErrorNotReady) HIP_OK(e);
     if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > 2000) break;
   }
-  KHIP(hipStreamSynchronize(st));
+  HIP_OK(hipStreamSynchronize(st));
 }
 
 // the solve chain on the handle's stream, device vectors in natural order (d_rhs is not modified; d_x may alias it)
@@ -1011,10 +957,10 @@ static void kwait(hipStream_t st) {
 // wide borders: the border terms summed by a grid, then across its workgroups; the border kernels read one slot
 template <bool RHS>
 static void border_terms_device(pc_kkt* k) {
-  if (!k->border_blocks) return;
+  if (!k->s.border_blocks) return;
   const int n_entries = RHS ? k->nb : k->nb * k->nb;
-  hipLaunchKernelGGL(kkt_border_terms<RHS>, dim3(k->border_blocks), dim3(256), 0, k->stream, k->args, k->border_part.p);
-  hipLaunchKernelGGL(kkt_border_terms_sum, dim3(n_entries), dim3(64), 0, k->stream, k->border_part.p, n_entries, k->border_blocks);
+  hipLaunchKernelGGL(kkt_border_terms<RHS>, dim3(k->s.border_blocks), dim3(256), 0, k->stream, k->args, k->border_part.p);
+  hipLaunchKernelGGL(kkt_border_terms_sum, dim3(n_entries), dim3(64), 0, k->stream, k->border_part.p, n_entries, k->s.border_blocks);
 }
 
 // the chain's levels on the handle's stream: one launch per level with many nodes, one launch for all the last ones
@@ -1025,16 +971,16 @@ static void cr_levels_device(pc_kkt* k) {
   // (the factorisation keeps a launch per level: its node kernel under a 1 024-thread workgroup's register budget measured
   //  9 % slower at config 3 -- 0.65 -> 0.71 ms -- and no faster at config 2; the two substitutions gain 5-8 % at config 2 and
   //  lose nothing at config 3, profiles/r04_ipm_iter_time.txt)
-  const size_t L = k->cr_lvl_ptr.size(), from = KIND == 0 ? L : k->cr_top_from;
+  const size_t L = k->s.cr_lvl_ptr.size(), from = KIND == 0 ? L : k->s.cr_top_from;
   auto level = [&](size_t l) {
-    const int64_t first = k->cr_lvl_ptr[l - 1], cnt = k->cr_lvl_ptr[l] - first;
+    const int64_t first = k->s.cr_lvl_ptr[l - 1], cnt = k->s.cr_lvl_ptr[l] - first;
     if (cnt <= 0) return;
-    if (KIND == 0) hipLaunchKernelGGL(kkt_cr_factor, dim3((unsigned)cnt), dim3(64), k->lds_cr, st, k->args, first);
-    else if (KIND == 1) hipLaunchKernelGGL(kkt_cr_forward, dim3((unsigned)cnt), dim3(64), k->lds_cr, st, k->args, first);
+    if (KIND == 0) hipLaunchKernelGGL(kkt_cr_factor, dim3((unsigned)cnt), dim3(64), k->s.lds_cr, st, k->args, first);
+    else if (KIND == 1) hipLaunchKernelGGL(kkt_cr_forward, dim3((unsigned)cnt), dim3(64), k->s.lds_cr, st, k->args, first);
     else hipLaunchKernelGGL(kkt_cr_backward, dim3((unsigned)cnt), dim3(64), 0, st, k->args, first);
   };
   auto top = [&] {
-    if (from < L) hipLaunchKernelGGL(kkt_cr_top<KIND>, dim3(1), dim3(64 * k->cr_top_waves), k->cr_top_lds, st, k->args, k->cr_top);
+    if (from < L) hipLaunchKernelGGL(kkt_cr_top<KIND>, dim3(1), dim3(64 * k->s.cr_top_waves), k->s.cr_top_lds, st, k->args, k->s.cr_top);
   };
   if (KIND == 2) {
     top();
@@ -1050,32 +996,30 @@ static void forward_device(pc_kkt* k, const double* d_rhs) {
   const unsigned nbk = (unsigned)((k->nu + 255) / 256);
   hipLaunchKernelGGL(kkt_perm_in, dim3(nbk), dim3(256), 0, st, d_rhs, k->perm.p, k->fixed.p, k->r.p, k->nu);
   if (k->n_leaf) {
-    // (two waves and the leaf in LDS: pc_kkt_solve 0.199 -> 0.183 ms at config 2, 0.425 -> 0.410 at config 3; with the shuttle's
-    //  6 000 leaves the LDS costs occupancy and the solve got slower, 0.63 -> 0.65-0.71: staged up to 4 096 leaves)
-    const int stage = k->leaf_fwd_env >= 0 ? k->leaf_fwd_env : (k->n_leaf <= 4096 ? 2 : 0);
+    const int stage = pck::leaf_forward_stage(k->s);
     k->leaf_forward_stage = stage;
     KArgs la = k->args;
-    la.lds_doubles = stage ? k->lds_leaf_full / 8 : 0;     // (0: solve from device memory, the A/B switch)
-    hipLaunchKernelGGL(kkt_leaf_forward, dim3(k->n_leaf), dim3(stage > 1 ? 64 * stage : 64), stage ? k->lds_leaf_full : k->lds_leaf, st, la);
+    la.lds_doubles = stage ? k->s.lds_leaf_full / 8 : 0;     // (0: solve from device memory, the A/B switch)
+    hipLaunchKernelGGL(kkt_leaf_forward, dim3(k->n_leaf), dim3(stage > 1 ? 64 * stage : 64), stage ? k->s.lds_leaf_full : k->s.lds_leaf, st, la);
   }
-  if (k->chain_cr) cr_levels_device<1>(k);
-  else if (k->n_phase) hipLaunchKernelGGL(kkt_chain_forward, dim3(k->n_phase), dim3(64), k->lds_chain, st, k->args);
+  if (k->s.chain_cr) cr_levels_device<1>(k);
+  else if (k->n_phase) hipLaunchKernelGGL(kkt_chain_forward, dim3(k->n_phase), dim3(64), k->s.lds_chain, st, k->args);
 }
 static void backward_device(pc_kkt* k, double* d_x);
 static void solve_device(pc_kkt* k, const double* d_rhs, double* d_x) {
   forward_device(k, d_rhs);
   border_terms_device<true>(k);
-  hipLaunchKernelGGL(kkt_border_solve<true>, dim3(1), dim3(256), k->lds_border, k->stream, k->args);
+  hipLaunchKernelGGL(kkt_border_solve<true>, dim3(1), dim3(256), k->s.lds_border, k->stream, k->args);
   backward_device(k, d_x);
 }
 static void backward_device(pc_kkt* k, double* d_x) {
   hipStream_t st = k->stream;
   const unsigned nbk = (unsigned)((k->nu + 255) / 256);
-  if (k->chain_cr) cr_levels_device<2>(k);
+  if (k->s.chain_cr) cr_levels_device<2>(k);
   else if (k->n_phase) hipLaunchKernelGGL(kkt_chain_backward, dim3(k->n_phase), dim3(64), 0, st, k->args);
   if (k->n_leaf) hipLaunchKernelGGL(kkt_leaf_backward, dim3(k->n_leaf), dim3(64), 0, st, k->args);
   hipLaunchKernelGGL(kkt_perm_out, dim3(nbk), dim3(256), 0, st, k->r.p, k->perm.p, d_x, k->nu);
-  KHIP(hipGetLastError());
+  HIP_OK(hipGetLastError());
 }
 
 // y = K x (MODE 0) or y = b - K x (MODE 1) on the handle's stream, device vectors
@@ -1085,28 +1029,40 @@ static void matvec_device(pc_kkt* k, int use_hess, const double* d_dvec, const d
   const int64_t threads = k->nu * MV_LANES;
   hipLaunchKernelGGL(kkt_matvec<MODE>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, k->mv_ptr.p, k->mv_col.p,
                      k->mv_src.p, k->mv_coef.p, k->d_G, k->d_H, use_hess, k->fixed.p, d_dvec, d_x, d_b, d_y, k->nu);
-  if (k->n_mv_long) {
-    hipLaunchKernelGGL(kkt_matvec_long, dim3((unsigned)k->n_mv_chunks), dim3(256), 0, st, k->mv_chunk_e0.p, k->mv_chunk_e1.p,
+  if (k->s.n_mv_long) {
+    hipLaunchKernelGGL(kkt_matvec_long, dim3((unsigned)k->s.n_mv_chunks), dim3(256), 0, st, k->mv_chunk_e0.p, k->mv_chunk_e1.p,
                        k->mv_col.p, k->mv_src.p, k->mv_coef.p, k->d_G, k->d_H, use_hess, d_x, k->mv_long_part.p);
-    hipLaunchKernelGGL(kkt_matvec_long_finish<MODE>, dim3((unsigned)((k->n_mv_long + 63) / 64)), dim3(64), 0, st, k->mv_long.p,
-                       k->mv_long_c0.p, k->n_mv_long, k->mv_long_part.p, k->fixed.p, d_dvec, d_x, d_b, d_y);
+    hipLaunchKernelGGL(kkt_matvec_long_finish<MODE>, dim3((unsigned)((k->s.n_mv_long + 63) / 64)), dim3(64), 0, st, k->mv_long.p,
+                       k->mv_long_c0.p, k->s.n_mv_long, k->mv_long_part.p, k->fixed.p, d_dvec, d_x, d_b, d_y);
   }
-  KHIP(hipGetLastError());
+  HIP_OK(hipGetLastError());
 }
 
 extern "C" {
 
 const char* pc_kkt_last_error(void) { return k_err.c_str(); }
 
+// the knobs a handle is built with: the PYCOLLO_AMD_KKT_* environment over the defaults
+static pck::Knobs knobs_from_env() {
+  pck::Knobs kn;
+  if (const char* env = std::getenv("PYCOLLO_AMD_KKT_RESID_TOL")) kn.resid_tol = std::atof(env);
+  if (const char* env = std::getenv("PYCOLLO_AMD_KKT_LEAF_FWD_LDS")) kn.leaf_fwd = std::atoi(env);
+  if (const char* env = std::getenv("PYCOLLO_AMD_KKT_LEAF_WAVES")) kn.leaf_waves = std::max(1, std::min(16, std::atoi(env)));
+  if (const char* env = std::getenv("PYCOLLO_AMD_KKT_CR")) kn.cr = std::atoi(env) != 0;
+  if (const char* env = std::getenv("PYCOLLO_AMD_KKT_CR_TOP")) kn.cr_top_cap = std::max(0, std::atoi(env));   // (0 / 1: off)
+  return kn;
+}
+
 int pc_kkt_create(const pc_kkt_desc* d, const double* d_jac, const double* d_hess, int device, pc_kkt** out) {
   if (out) *out = nullptr;
   pc_kkt* k = nullptr;
-  const int ok = guarded([&] {
+  const int ok = guarded(k_err, [&] {
     if (!d || !out || !d_jac || !d_hess) throw std::runtime_error("null argument");
-    KHIP(hipSetDevice(device));
+    pck::Shape shape = pck::build_shape(*d, knobs_from_env());   // (every refusal: before anything is allocated)
+    HIP_OK(hipSetDevice(device));
     k = new pc_kkt();
     k->device = device;
-    KHIP(hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking));
+    HIP_OK(hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking));
     k->stream = k->own_stream;
     k->d_G = d_jac;
     k->d_H = d_hess;
@@ -1117,6 +1073,9 @@ int pc_kkt_create(const pc_kkt_desc* d, const double* d_jac, const double* d_hes
     k->nb = (int)d->nb;
     k->n_dst = d->n_dst;
     k->total = d->total_vals;
+    k->s = std::move(shape);
+    pck::Shape& s = k->s;
+    // the descriptor's tables
     k->perm.upload(d->perm, d->nu);
     k->leaf_ptr.upload(d->leaf_ptr, d->n_leaf + 1);
     k->chain_ptr.upload(d->chain_ptr, d->n_chain + 1);
@@ -1135,160 +1094,47 @@ int pc_kkt_create(const pc_kkt_desc* d, const double* d_jac, const double* d_hes
     k->fixed.upload(d->fixed, d->nu);
     k->mv_ptr.upload(d->mv_ptr, d->nu + 1);
     k->mv_col.upload(d->mv_col, d->n_mv);
-    {
-      std::vector<uint32_t> srcw((size_t)d->n_mv);
-      for (int64_t e = 0; e < d->n_mv; ++e) {
-        if (d->mv_idx[e] < 0 || d->mv_idx[e] >= (1 << 30) || d->mv_kind[e] < 0 || d->mv_kind[e] > 2)
-          throw std::runtime_error("matvec table entry out of range");
-        srcw[e] = ((uint32_t)d->mv_kind[e] << 30) | (uint32_t)d->mv_idx[e];
-      }
-      k->mv_src.upload(srcw.data(), srcw.size());
-      std::vector<int64_t> longs, c0{0}, ce0, ce1;
-      for (int64_t r = 0; r < d->nu; ++r)
-        if (d->mv_ptr[r + 1] - d->mv_ptr[r] > MV_LONG) {
-          longs.push_back(r);
-          for (int64_t e = d->mv_ptr[r]; e < d->mv_ptr[r + 1]; e += MV_CHUNK) {
-            ce0.push_back(e);
-            ce1.push_back(std::min<int64_t>(e + MV_CHUNK, d->mv_ptr[r + 1]));
-          }
-          c0.push_back((int64_t)ce0.size());
-        }
-      k->n_mv_long = (int64_t)longs.size();
-      k->n_mv_chunks = (int64_t)ce0.size();
-      k->mv_long.upload(longs.data(), longs.size());
-      k->mv_long_c0.upload(c0.data(), c0.size());
-      k->mv_chunk_e0.upload(ce0.data(), ce0.size());
-      k->mv_chunk_e1.upload(ce1.data(), ce1.size());
-      k->mv_long_part.alloc((size_t)std::max<int64_t>(1, k->n_mv_chunks));
-    }
     k->mv_coef.upload(d->mv_coef, d->n_mv);
-    for (auto* w : {&k->w_rhs, &k->w_sol, &k->w_res, &k->w_trial, &k->w_dx, &k->w_dvec}) w->alloc((size_t)d->nu);
-    k->w_part.alloc(4 * 256);
-    k->w_norm.alloc(4);
-    k->h_norm.alloc(4);
-    if (const char* env = std::getenv("PYCOLLO_AMD_KKT_RESID_TOL")) k->resid_tol = std::atof(env);
-    if (const char* env = std::getenv("PYCOLLO_AMD_KKT_LEAF_FWD_LDS")) k->leaf_fwd_env = std::atoi(env);
-    if (const char* env = std::getenv("PYCOLLO_AMD_KKT_LEAF_WAVES")) k->leaf_waves = std::max(1, std::min(16, std::atoi(env)));
-    // derived tables
-    std::vector<uint8_t> last(d->n_chain, 0);
-    for (int64_t p = 0; p < d->n_phase; ++p) last[d->chain_phase_ptr[p + 1] - 1] = 1;
-    std::vector<int64_t> leaf_of_left(d->n_chain, -1), leafG_off(d->n_leaf), chainG_off(d->n_chain);
-    int64_t og = 0, mmax = 1, wmax = 1, nzmax = 1, wcmax = 1;
-    for (int64_t l = 0; l < d->n_leaf; ++l) {
-      const int64_t left = d->leaf_left[l];
-      leaf_of_left[left] = l;
-      const int64_t m = d->leaf_ptr[l + 1] - d->leaf_ptr[l];
-      const int64_t w = (d->chain_ptr[left + 1] - d->chain_ptr[left]) + (d->chain_ptr[left + 2] - d->chain_ptr[left + 1]) + d->nb;
-      leafG_off[l] = og;
-      og += w;
-      mmax = std::max(mmax, m);
-      wmax = std::max(wmax, w);
+    // the shape's tables
+    k->mv_src.upload(s.mv_src);
+    s.mv_src = {};   // (one word per entry of the product: the only table of the shape that is large, and nothing reads it again)
+    k->mv_long.upload(s.mv_long);
+    k->mv_long_c0.upload(s.mv_long_c0);
+    k->mv_chunk_e0.upload(s.mv_chunk_e0);
+    k->mv_chunk_e1.upload(s.mv_chunk_e1);
+    k->chain_last.upload(s.chain_last);
+    k->leaf_of_left.upload(s.leaf_of_left);
+    k->leafG_off.upload(s.leafG_off);
+    k->chainG_off.upload(s.chainG_off);
+    if (s.chain_cr) {
+      const CrPlan& P = s.cr;
+      k->cr_a.upload(P.ca); k->cr_b.upload(P.cb);
+      k->cr_mid_a.upload(P.mida); k->cr_mid_b.upload(P.midb);
+      k->pull_ptr.upload(P.pull_ptr); k->pull_e.upload(P.pull_e);
+      k->chain_first.upload(P.first);
+      if (s.any_export) k->chain_export.upload(P.exported);
+      k->crP_off.upload(P.oP); k->crS_off.upload(P.oS); k->crG_off.upload(P.oG);
+      k->cr_nodes.upload(s.cr_nodes);
+      k->crbuf.alloc((size_t)s.n_crbuf);
+      k->h_chain_ptr.assign(d->chain_ptr, d->chain_ptr + d->n_chain + 1);
     }
-    k->leafG.alloc((size_t)std::max<int64_t>(1, og));
-    og = 0;
-    for (int64_t c = 0; c < d->n_chain; ++c) {
-      const int64_t nz = d->chain_ptr[c + 1] - d->chain_ptr[c];
-      const int64_t nx = last[c] ? 0 : d->chain_ptr[c + 2] - d->chain_ptr[c + 1];
-      if (!last[c] && leaf_of_left[c] < 0) throw std::runtime_error("chain node without a leaf on its right");
-      chainG_off[c] = og;
-      og += nx + d->nb;
-      nzmax = std::max(nzmax, nz);
-      wcmax = std::max(wcmax, nx + d->nb);
-    }
-    k->chainG.alloc((size_t)std::max<int64_t>(1, og));
-    k->chain_last.upload(last.data(), last.size());
-    k->leaf_of_left.upload(leaf_of_left.data(), leaf_of_left.size());
-    k->leafG_off.upload(leafG_off.data(), leafG_off.size());
-    k->chainG_off.upload(chainG_off.data(), chainG_off.size());
-    k->lds_leaf = (int)(8 * (2 * mmax + wmax + 2));
-    {
-      int64_t want = 0;
-      for (int64_t l = 0; l < d->n_leaf; ++l) {
-        const int64_t left = d->leaf_left[l], m = d->leaf_ptr[l + 1] - d->leaf_ptr[l];
-        const int64_t w = (d->chain_ptr[left + 1] - d->chain_ptr[left]) + (d->chain_ptr[left + 2] - d->chain_ptr[left + 1]) + d->nb;
-        const int64_t need = 8 * (m * (m + w) + 2 * m + w + 2);
-        if (need <= 64000) want = std::max(want, need);
-      }
-      k->lds_leaf_full = (int)std::max<int64_t>(want, k->lds_leaf);
-    }
-    k->lds_chain = (int)(8 * (2 * nzmax + wcmax + 2));
-    {
-      const int64_t full = 8 * (2 * nzmax + wcmax + 2 * wcmax * wcmax + nzmax * (nzmax + wcmax) + 2);
-      k->args.nzmax = (int32_t)nzmax;
-      k->args.wcmax = (int32_t)wcmax;
-      k->args.chain_lds = full <= 64000 ? 1 : 0;
-      k->lds_chain_factor = (int)(k->args.chain_lds ? full : k->lds_chain);
-    }
-    {   // cyclic reduction of the chain: levels, separators, what every node pulls from the levels below (pc_kkt_cr.hpp)
-      const int64_t nc = d->n_chain;
-      CrPlan P;
-      cr_build(nc, d->n_phase, d->chain_phase_ptr, d->chain_ptr, d->nb, d->chain_export, P);
-      k->chain_cr = P.ldsmax <= 64000 && P.max_pull <= CR_MAX_PULL;
-      if (const char* env = std::getenv("PYCOLLO_AMD_KKT_CR")) k->chain_cr = k->chain_cr && std::atoi(env) != 0;
-      if (P.any_export && !k->chain_cr) throw std::runtime_error("exported chain nodes need the cyclic-reduction kernels (blocks too large for their LDS)");
-      k->any_export = P.any_export;
-      if (k->chain_cr) {
-        std::vector<int64_t> nodes;
-        k->cr_lvl_ptr.assign(1, 0);
-        for (int l = 1; l <= P.lmax; ++l) {
-          for (int64_t c = 0; c < nc; ++c)
-            if (P.lvl[c] == l) nodes.push_back(c);
-          k->cr_lvl_ptr.push_back((int64_t)nodes.size());
-        }
-        k->lds_cr = (int)P.ldsmax;
-        {   // the last levels in one launch (kkt_cr_top): as many trailing levels as hold at most two nodes per wave
-          const size_t L = k->cr_lvl_ptr.size();
-          const int wave_bytes = (int)(((int64_t)P.ldsmax + 24 * CR_MAX_PULL + 15) & ~(int64_t)15);
-          int nw = (int)std::min<int64_t>(16, 65536 / wave_bytes);
-          if (const char* env = std::getenv("PYCOLLO_AMD_KKT_CR_TOP")) nw = std::min(nw, std::atoi(env));   // (0 / 1: off)
-          size_t from = L;
-          if (nw >= 2) {
-            while (from > 1 && k->cr_lvl_ptr[from - 1] - k->cr_lvl_ptr[from - 2] <= nw && L - (from - 1) <= 17) --from;
-            if (L - from < 2) from = L;             // (a single level gains nothing over its own launch)
-          }
-          k->cr_top_from = from;
-          k->cr_top_waves = nw;
-          k->cr_top_lds = nw * wave_bytes;
-          k->cr_top.n = (int32_t)(L - from);
-          k->cr_top.wave_bytes = wave_bytes;
-          for (size_t i = 0; from + i <= L && i < 18; ++i) k->cr_top.ptr[i] = k->cr_lvl_ptr[from - 1 + i];
-        }
-        k->crbuf.alloc((size_t)std::max<int64_t>(1, P.buf_len));
-        k->cr_a.upload(P.ca.data(), P.ca.size()); k->cr_b.upload(P.cb.data(), P.cb.size());
-        k->cr_mid_a.upload(P.mida.data(), P.mida.size()); k->cr_mid_b.upload(P.midb.data(), P.midb.size());
-        k->pull_ptr.upload(P.pull_ptr.data(), P.pull_ptr.size()); k->pull_e.upload(P.pull_e.data(), P.pull_e.size());
-        k->chain_first.upload(P.first.data(), P.first.size());
-        if (P.any_export) {
-          k->chain_export.upload(P.exported.data(), P.exported.size());
-          for (int64_t c = 0; c < nc; ++c)
-            if (P.exported[c]) k->export_nodes.push_back(c);
-        }
-        k->crP_off.upload(P.oP.data(), P.oP.size()); k->crS_off.upload(P.oS.data(), P.oS.size()); k->crG_off.upload(P.oG.data(), P.oG.size());
-        k->h_crP_off = P.oP;
-        k->h_cr_b = P.cb;
-        k->h_chain_ptr.assign(d->chain_ptr, d->chain_ptr + nc + 1);
-        k->cr_nodes.upload(nodes.data(), nodes.size());
-      }
-    }
-    k->lds_border = (int)(8 * (2 * (int64_t)d->nb + 2 + 256));
-    // (also the NLP's own narrow border once there are thousands of terms: the one workgroup's walk took 93 us per
-    //  factorisation and 40 us per back-substitution at config 3, 2 x 2 entries x 5 001 terms; config 2's 1 001 terms stay)
-    if (d->nb > 0 && ((int64_t)d->nb * d->nb * (d->n_leaf + d->n_chain) > ((int64_t)1 << 18) || d->n_leaf + d->n_chain >= 2048)) {
-      k->border_blocks = (int)std::min<int64_t>(256, d->n_leaf + d->n_chain);
-      k->border_part.alloc((size_t)k->border_blocks * d->nb * d->nb);
-    }
-    if (k->lds_leaf > 60000 || k->lds_chain > 60000 || k->lds_border > 60000)
-      throw std::runtime_error("KKT block too large for the solver's LDS staging");
-    k->vals.alloc((size_t)d->total_vals);
-    k->r.alloc((size_t)d->nu);
-    k->dvec.alloc((size_t)d->nu);
-    k->vin.alloc((size_t)d->nu);
-    k->vout.alloc((size_t)d->nu);
-    k->counts.alloc((size_t)2 * (d->n_leaf + d->n_chain + 1));
-    k->h_counts.alloc((size_t)2 * (d->n_leaf + d->n_chain + 1));
-    k->h_a.alloc((size_t)d->nu);
-    k->h_b.alloc((size_t)d->nu);
+    // scratch
+    k->mv_long_part.alloc((size_t)s.n_mv_long_part);
+    for (auto* w : {&k->w_rhs, &k->w_sol, &k->w_res, &k->w_trial, &k->w_dx, &k->w_dvec, &k->r, &k->dvec, &k->vin, &k->vout})
+      w->alloc((size_t)s.n_vec);
+    k->w_part.alloc((size_t)s.n_norm_part);
+    k->w_norm.alloc((size_t)s.n_norm);
+    k->h_norm.alloc((size_t)s.n_norm);
+    k->leafG.alloc((size_t)s.n_leafG);
+    k->chainG.alloc((size_t)s.n_chainG);
+    k->border_part.alloc((size_t)s.n_border_part);
+    k->vals.alloc((size_t)s.n_vals);
+    k->counts.alloc((size_t)s.n_counts);
+    k->h_counts.alloc((size_t)s.n_counts);
+    k->h_a.alloc((size_t)s.n_vec);
+    k->h_b.alloc((size_t)s.n_vec);
     KArgs& a = k->args;
+    a.nzmax = s.nzmax; a.wcmax = s.wcmax; a.chain_lds = s.chain_lds;
     a.vals = k->vals.p;
     a.leaf_ptr = k->leaf_ptr.p; a.chain_ptr = k->chain_ptr.p; a.chain_phase_ptr = k->chain_phase_ptr.p;
     a.leaf_left = k->leaf_left.p; a.leafA_off = k->leafA_off.p; a.leafS_off = k->leafS_off.p;
@@ -1302,9 +1148,9 @@ int pc_kkt_create(const pc_kkt_desc* d, const double* d_jac, const double* d_hes
     a.r = k->r.p; a.leafG = k->leafG.p; a.chainG = k->chainG.p;
     a.leafG_off = k->leafG_off.p; a.chainG_off = k->chainG_off.p;
     a.border_part = k->border_part.p;
-    a.border_part_blocks = k->border_blocks ? 1 : 0;   // (the border kernels read the slot kkt_border_terms_sum leaves)
-    a.cr = k->chain_cr ? 1 : 0;
-    if (k->chain_cr) {
+    a.border_part_blocks = s.border_blocks ? 1 : 0;   // (the border kernels read the slot kkt_border_terms_sum leaves)
+    a.cr = s.chain_cr ? 1 : 0;
+    if (s.chain_cr) {
       a.crbuf = k->crbuf.p;
       a.cr_a = k->cr_a.p; a.cr_b = k->cr_b.p;
       a.crP_off = k->crP_off.p; a.crS_off = k->crS_off.p; a.crG_off = k->crG_off.p;
@@ -1312,7 +1158,7 @@ int pc_kkt_create(const pc_kkt_desc* d, const double* d_jac, const double* d_hes
       a.cr_mid_a = k->cr_mid_a.p; a.cr_mid_b = k->cr_mid_b.p;
       a.pull_ptr = k->pull_ptr.p; a.pull_e = k->pull_e.p;
       a.chain_first = k->chain_first.p;
-      a.chain_export = k->any_export ? k->chain_export.p : nullptr;
+      a.chain_export = s.any_export ? k->chain_export.p : nullptr;
       // (every table the level kernels dereference must be in device memory before the first launch: a forgotten upload is a
       //  null read on the GPU, not an error code)
       if (d->n_chain > 0) {
@@ -1320,17 +1166,25 @@ int pc_kkt_create(const pc_kkt_desc* d, const double* d_jac, const double* d_hes
                               a.pull_ptr, a.pull_e, a.chain_first, a.chain_last, a.chain_ptr, a.chainD_off};
         for (const void* q : need)
           if (!q) throw std::runtime_error("internal: a cyclic-reduction table was not uploaded");
-        if ((int64_t)k->cr_nodes.n != d->n_chain || k->cr_lvl_ptr.back() != d->n_chain)
-          throw std::runtime_error("internal: the level lists do not cover the chain");
       }
     }
   });
   if (!ok) {
-    delete k;
+    release(k);
     return 0;
   }
   *out = k;
   return 1;
+}
+
+// Host-only (no device): pc_kkt_info as a fresh handle on this descriptor would report it, with what its first solve will
+// pick in leaf_forward_stage -- the shape decisions for the CPU tests.
+int pc_kkt_shape_info(const pc_kkt_desc* d, pc_kkt_info* out) {
+  return guarded(k_err, [&] {
+    if (!d || !out) throw std::runtime_error("null argument");
+    const pck::Shape s = pck::build_shape(*d, knobs_from_env());
+    pck::fill_info(s, s.n_leaf ? pck::leaf_forward_stage(s) : -1, out);
+  });
 }
 
 // Host integer work (no device): where in the value buffer the entry K[u, v] of the blocked matrix lives, for n pairs
@@ -1374,7 +1228,7 @@ static inline int64_t plan_position(const pc_kkt_plan* P, int64_t a, int64_t b) 
 int pc_kkt_cr_plan(int64_t n_chain, int64_t n_phase, const int64_t* chain_phase_ptr, const int64_t* chain_ptr, int64_t nb,
                    const uint8_t* chain_export, int64_t* cr_a, int64_t* cr_b, int64_t* mid_a, int64_t* mid_b, int32_t* level,
                    int64_t* pull_ptr, int32_t* pull_e, int64_t pull_cap) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!chain_phase_ptr || !chain_ptr || !cr_a || !cr_b || !mid_a || !mid_b || !level || !pull_ptr || !pull_e)
       throw std::runtime_error("null argument");
     CrPlan P;
@@ -1389,7 +1243,7 @@ int pc_kkt_cr_plan(int64_t n_chain, int64_t n_phase, const int64_t* chain_phase_
 }
 
 int pc_kkt_plan_positions(const pc_kkt_plan* P, int64_t n, const int64_t* u, const int64_t* v, int64_t* out) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!P || !u || !v || !out || n < 0) throw std::runtime_error("null argument");
     for (int64_t e = 0; e < n; ++e) out[e] = plan_position(P, u[e], v[e]);
   });
@@ -1406,7 +1260,7 @@ int pc_kkt_plan_entries(const pc_kkt_plan* P, int64_t n, int64_t nv, int64_t nH,
                         const int64_t* ineq_rows, const uint8_t* fixed, int64_t* counts, int64_t* dst, int64_t* run_ptr,
                         int32_t* src_kind, int32_t* src_idx, double* src_coef, int64_t* mv_ptr, int32_t* mv_col,
                         int32_t* mv_kind, int32_t* mv_idx, double* mv_coef) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!P || !counts || !fixed || (nH && (!hr || !hc)) || (nG && (!jr || !jc || !row_scale)) || (ns && !ineq_rows))
       throw std::runtime_error("null argument");
     struct Ent { int64_t d, u, v; int32_t kind, idx; double coef; };
@@ -1492,34 +1346,13 @@ int pc_kkt_plan_entries(const pc_kkt_plan* P, int64_t n, int64_t nv, int64_t nH,
 }
 
 int pc_kkt_get_info(const pc_kkt* k, pc_kkt_info* info) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !info) throw std::runtime_error("null argument");
-    std::memset(info, 0, sizeof(*info));
-    info->n_leaf = k->n_leaf;
-    info->n_chain = k->n_chain;
-    info->nb = k->nb;
-    info->n_mv_long = k->n_mv_long;
-    info->chain_cr = k->chain_cr ? 1 : 0;
-    info->cr_levels = k->chain_cr ? (int32_t)k->cr_lvl_ptr.size() - 1 : 0;
-    info->cr_top_levels = k->chain_cr ? k->cr_top.n : 0;
-    info->cr_top_waves = k->chain_cr ? k->cr_top_waves : 0;
-    info->border_blocks = k->border_blocks;
-    info->leaf_forward_stage = k->leaf_forward_stage;
-    info->leaf_waves = k->leaf_waves;
+    pck::fill_info(k->s, k->leaf_forward_stage, info);
   });
 }
 
-void pc_kkt_destroy(pc_kkt* k) {
-  if (!k) return;
-  (void)hipSetDevice(k->device);
-
-  if (k->stream) {
-    (void)hipStreamSynchronize(k->stream);
-    (void)hipStreamSynchronize(k->stream);
-    (void)hipStreamDestroy(k->own_stream);
-  }
-  delete k;
-}
+void pc_kkt_destroy(pc_kkt* k) { release(k); }
 
 // assembly + factorisation on the handle's stream with the diagonal in device memory; the pivot signs come back
 // border_mode: kkt_border_factor's MODE (0: the whole factorisation; 1: leaves and chain only, the border block left
@@ -1527,7 +1360,7 @@ void pc_kkt_destroy(pc_kkt* k) {
 static void factor_device(pc_kkt* k, int use_hess, const double* d_dvec, int32_t* n_pos, int32_t* n_neg, int border_mode = 0) {
   {
     hipStream_t st = k->stream;
-    KHIP(hipMemsetAsync(k->vals.p, 0, (size_t)k->total * sizeof(double), st));
+    HIP_OK(hipMemsetAsync(k->vals.p, 0, (size_t)k->total * sizeof(double), st));
     if (k->n_dst)
       hipLaunchKernelGGL(kkt_scatter, dim3((unsigned)((k->n_dst + 255) / 256)), dim3(256), 0, st, k->vals.p, k->dst.p, k->run_ptr.p,
                          k->src_kind.p, k->src_idx.p, k->src_coef.p, k->d_G, k->d_H, use_hess, k->n_dst);
@@ -1535,19 +1368,16 @@ static void factor_device(pc_kkt* k, int use_hess, const double* d_dvec, int32_t
                        d_dvec, k->nu);
     if (k->n_leaf) {
       KArgs la = k->args;
-      la.lds_doubles = k->lds_leaf_full / 8;
-      // four waves per leaf: 0.246 -> 0.221 ms per factorisation at config 2, 0.644 -> 0.594 at config 3 against two (the
-      // trailing update of a pivot step is the parallel part); one wave with LDS-only ordering 0.30 / 0.75, six or eight waves
-      // no better than four and 4 % worse on the shuttle's blocks (profiles/r04_ipm_iter_time.txt)
-      hipLaunchKernelGGL(kkt_leaf_factor, dim3(k->n_leaf), dim3(64 * k->leaf_waves), k->lds_leaf_full, st, la);
+      la.lds_doubles = k->s.lds_leaf_full / 8;
+      hipLaunchKernelGGL(kkt_leaf_factor, dim3(k->n_leaf), dim3(64 * k->s.knobs.leaf_waves), k->s.lds_leaf_full, st, la);
     }
-    if (k->chain_cr) cr_levels_device<0>(k);
-    else if (k->n_phase) hipLaunchKernelGGL(kkt_chain_factor, dim3(k->n_phase), dim3(64), k->lds_chain_factor, st, k->args);
+    if (k->s.chain_cr) cr_levels_device<0>(k);
+    else if (k->n_phase) hipLaunchKernelGGL(kkt_chain_factor, dim3(k->n_phase), dim3(64), k->s.lds_chain_factor, st, k->args);
     border_terms_device<false>(k);
-    if (border_mode == 0) hipLaunchKernelGGL(kkt_border_factor<0>, dim3(1), dim3(256), k->lds_border, st, k->args);
-    else hipLaunchKernelGGL(kkt_border_factor<1>, dim3(1), dim3(256), k->lds_border, st, k->args);
-    KHIP(hipGetLastError());
-    KHIP(hipMemcpyAsync(k->h_counts.p, k->counts.p, k->h_counts.n * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (border_mode == 0) hipLaunchKernelGGL(kkt_border_factor<0>, dim3(1), dim3(256), k->s.lds_border, st, k->args);
+    else hipLaunchKernelGGL(kkt_border_factor<1>, dim3(1), dim3(256), k->s.lds_border, st, k->args);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(k->h_counts.p, k->counts.p, k->h_counts.n * sizeof(int), hipMemcpyDeviceToHost, st));
     kwait(st);
     int64_t p = 0, q = 0;
     const size_t n_counts = border_mode == 0 ? k->h_counts.n : k->h_counts.n - 2;   // (the last pair is the border's)
@@ -1562,11 +1392,10 @@ static void factor_device(pc_kkt* k, int use_hess, const double* d_dvec, int32_t
 }
 
 int pc_kkt_factor(pc_kkt* k, int use_hess, const double* dvec, int32_t* n_pos, int32_t* n_neg) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !dvec) throw std::runtime_error("null argument");
-    KHIP(hipSetDevice(k->device));
-    std::memcpy(k->h_a.p, dvec, k->nu * sizeof(double));
-    KHIP(hipMemcpyAsync(k->dvec.p, k->h_a.p, k->nu * sizeof(double), hipMemcpyHostToDevice, k->stream));
+    HIP_OK(hipSetDevice(k->device));
+    stage_up(k, dvec, k->h_a, k->dvec);
     factor_device(k, use_hess, k->dvec.p, n_pos, n_neg);
   });
 }
@@ -1578,32 +1407,31 @@ int pc_kkt_factor(pc_kkt* k, int use_hess, const double* dvec, int32_t* n_pos, i
 // handle has nothing else); pc_kkt_forward_partial / pc_kkt_backward_partial are the two halves of pc_kkt_solve around
 // the reduced solve.  Host vectors; the matrices stay on the device.
 int pc_kkt_factor_partial(pc_kkt* k, int use_hess, const double* dvec, double* border_out, int32_t* n_pos, int32_t* n_neg) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !dvec || !border_out) throw std::runtime_error("null argument");
-    KHIP(hipSetDevice(k->device));
-    std::memcpy(k->h_a.p, dvec, k->nu * sizeof(double));
-    KHIP(hipMemcpyAsync(k->dvec.p, k->h_a.p, k->nu * sizeof(double), hipMemcpyHostToDevice, k->stream));
+    HIP_OK(hipSetDevice(k->device));
+    stage_up(k, dvec, k->h_a, k->dvec);
     factor_device(k, use_hess, k->dvec.p, n_pos, n_neg, 1);
     if (k->nb) {
-      KHIP(hipMemcpyAsync(border_out, k->vals.p + k->args.border_off, (size_t)k->nb * k->nb * sizeof(double),
+      HIP_OK(hipMemcpyAsync(border_out, k->vals.p + k->args.border_off, (size_t)k->nb * k->nb * sizeof(double),
                           hipMemcpyDeviceToHost, k->stream));
-      KHIP(hipStreamSynchronize(k->stream));
+      HIP_OK(hipStreamSynchronize(k->stream));
     }
   });
 }
 
 int pc_kkt_border_load_factor(pc_kkt* k, const double* border, int32_t* n_pos, int32_t* n_neg) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !border) throw std::runtime_error("null argument");
-    KHIP(hipSetDevice(k->device));
+    HIP_OK(hipSetDevice(k->device));
     hipStream_t st = k->stream;
     if (k->nb)
-      KHIP(hipMemcpyAsync(k->vals.p + k->args.border_off, border, (size_t)k->nb * k->nb * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(kkt_border_factor<2>, dim3(1), dim3(256), k->lds_border, st, k->args);
-    KHIP(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(k->vals.p + k->args.border_off, border, (size_t)k->nb * k->nb * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(kkt_border_factor<2>, dim3(1), dim3(256), k->s.lds_border, st, k->args);
+    HIP_OK(hipGetLastError());
     int* cnt = k->counts.p + 2 * ((size_t)k->n_leaf + k->n_chain);
-    KHIP(hipMemcpyAsync(k->h_counts.p, cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    KHIP(hipStreamSynchronize(st));
+    HIP_OK(hipMemcpyAsync(k->h_counts.p, cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
     if (n_pos) *n_pos = k->h_counts.p[0];
     if (n_neg) *n_neg = k->h_counts.p[1];
     k->factored = true;
@@ -1611,34 +1439,31 @@ int pc_kkt_border_load_factor(pc_kkt* k, const double* border, int32_t* n_pos, i
 }
 
 int pc_kkt_forward_partial(pc_kkt* k, const double* rhs, double* border_rhs_out) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !rhs || !border_rhs_out) throw std::runtime_error("null argument");
     if (!k->factored) throw std::runtime_error("pc_kkt_forward_partial before a factorisation");
-    KHIP(hipSetDevice(k->device));
+    HIP_OK(hipSetDevice(k->device));
     hipStream_t st = k->stream;
-    std::memcpy(k->h_a.p, rhs, k->nu * sizeof(double));
-    KHIP(hipMemcpyAsync(k->vin.p, k->h_a.p, k->nu * sizeof(double), hipMemcpyHostToDevice, st));
+    stage_up(k, rhs, k->h_a, k->vin);
     forward_device(k, k->vin.p);
     border_terms_device<true>(k);
-    hipLaunchKernelGGL(kkt_border_solve<false>, dim3(1), dim3(256), k->lds_border, st, k->args);
-    KHIP(hipGetLastError());
-    if (k->nb) KHIP(hipMemcpyAsync(border_rhs_out, k->r.p + k->args.base_border, (size_t)k->nb * sizeof(double), hipMemcpyDeviceToHost, st));
-    KHIP(hipStreamSynchronize(st));
+    hipLaunchKernelGGL(kkt_border_solve<false>, dim3(1), dim3(256), k->s.lds_border, st, k->args);
+    HIP_OK(hipGetLastError());
+    if (k->nb) HIP_OK(hipMemcpyAsync(border_rhs_out, k->r.p + k->args.base_border, (size_t)k->nb * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
   });
 }
 
 int pc_kkt_backward_partial(pc_kkt* k, const double* border_x, double* x) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !border_x || !x) throw std::runtime_error("null argument");
     if (!k->factored) throw std::runtime_error("pc_kkt_backward_partial before a factorisation");
-    KHIP(hipSetDevice(k->device));
+    HIP_OK(hipSetDevice(k->device));
     hipStream_t st = k->stream;
-    if (k->nb) KHIP(hipMemcpyAsync(k->r.p + k->args.base_border, border_x, (size_t)k->nb * sizeof(double), hipMemcpyHostToDevice, st));
+    if (k->nb) HIP_OK(hipMemcpyAsync(k->r.p + k->args.base_border, border_x, (size_t)k->nb * sizeof(double), hipMemcpyHostToDevice, st));
     backward_device(k, k->vout.p);
-    KHIP(hipGetLastError());
-    KHIP(hipMemcpyAsync(k->h_b.p, k->vout.p, k->nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    KHIP(hipStreamSynchronize(st));
-    std::memcpy(x, k->h_b.p, k->nu * sizeof(double));
+    HIP_OK(hipGetLastError());
+    stage_down(k, k->vout.p, k->h_b, x);
   });
 }
 
@@ -1647,40 +1472,40 @@ int pc_kkt_backward_partial(pc_kkt* k, const double* border_x, double* x) {
 // (nr = 0 for a last node or when the segment's last node is not exported); after pc_kkt_forward_partial their right-hand
 // sides minus what the eliminated blocks owe them; before pc_kkt_backward_partial their solution from the reduced system.
 static void export_copy(pc_kkt* k, double* host, int what) {   // 0: panels out, 1: right-hand sides out, 2: solution in
-  KHIP(hipSetDevice(k->device));
+  HIP_OK(hipSetDevice(k->device));
   hipStream_t st = k->stream;
   size_t o = 0;
-  for (int64_t c : k->export_nodes) {
+  for (int64_t c : k->s.export_nodes) {
     const int64_t nz = k->h_chain_ptr[c + 1] - k->h_chain_ptr[c];
-    const int64_t b = k->h_cr_b[c], nr = b >= 0 ? k->h_chain_ptr[b + 1] - k->h_chain_ptr[b] : 0;
+    const int64_t b = k->s.cr.cb[c], nr = b >= 0 ? k->h_chain_ptr[b + 1] - k->h_chain_ptr[b] : 0;
     if (what == 0) {
       const size_t cnt = (size_t)(nz * (nz + nr + k->nb));
-      if (cnt) KHIP(hipMemcpyAsync(host + o, k->crbuf.p + k->h_crP_off[c], cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+      if (cnt) HIP_OK(hipMemcpyAsync(host + o, k->crbuf.p + k->s.cr.oP[c], cnt * sizeof(double), hipMemcpyDeviceToHost, st));
       o += cnt;
     } else {
       double* dev = k->r.p + k->args.base_chain + k->h_chain_ptr[c];
-      if (nz) KHIP(hipMemcpyAsync(what == 1 ? host + o : dev, what == 1 ? dev : host + o, (size_t)nz * sizeof(double),
+      if (nz) HIP_OK(hipMemcpyAsync(what == 1 ? host + o : dev, what == 1 ? dev : host + o, (size_t)nz * sizeof(double),
                                   what == 1 ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice, st));
       o += (size_t)nz;
     }
   }
-  KHIP(hipStreamSynchronize(st));
+  HIP_OK(hipStreamSynchronize(st));
 }
 int pc_kkt_export_panels(pc_kkt* k, double* out) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !out) throw std::runtime_error("null argument");
     if (!k->factored) throw std::runtime_error("pc_kkt_export_panels before a factorisation");
     export_copy(k, out, 0);
   });
 }
 int pc_kkt_export_rhs(pc_kkt* k, double* out) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !out) throw std::runtime_error("null argument");
     export_copy(k, out, 1);
   });
 }
 int pc_kkt_import_solution(pc_kkt* k, const double* in) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !in) throw std::runtime_error("null argument");
     export_copy(k, const_cast<double*>(in), 2);
   });
@@ -1688,58 +1513,49 @@ int pc_kkt_import_solution(pc_kkt* k, const double* in) {
 
 // ---- the same with every vector in device memory (the device-resident interior-point iteration, pc_ipm.hip) ----
 int pc_kkt_set_stream(pc_kkt* k, void* stream) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k) throw std::runtime_error("null argument");
-    KHIP(hipSetDevice(k->device));
-    KHIP(hipStreamSynchronize(k->stream));
+    HIP_OK(hipSetDevice(k->device));
+    HIP_OK(hipStreamSynchronize(k->stream));
     if (stream) k->stream = (hipStream_t)stream;   // (the handle's own stream stays allocated; it is destroyed with the handle)
   });
 }
 
 int pc_kkt_factor_device(pc_kkt* k, int use_hess, const double* d_dvec, int32_t* n_pos, int32_t* n_neg) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !d_dvec) throw std::runtime_error("null argument");
-    KHIP(hipSetDevice(k->device));
+    HIP_OK(hipSetDevice(k->device));
     factor_device(k, use_hess, d_dvec, n_pos, n_neg);
   });
 }
 
 int pc_kkt_matvec_device(pc_kkt* k, int use_hess, const double* d_dvec, const double* d_x, double* d_y) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !d_dvec || !d_x || !d_y) throw std::runtime_error("null argument");
-    KHIP(hipSetDevice(k->device));
+    HIP_OK(hipSetDevice(k->device));
     matvec_device<0>(k, use_hess, d_dvec, d_x, nullptr, d_y);
   });
 }
 
 int pc_kkt_solve(pc_kkt* k, const double* rhs, double* x) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !rhs || !x) throw std::runtime_error("null argument");
     if (!k->factored) throw std::runtime_error("pc_kkt_solve before pc_kkt_factor");
-    KHIP(hipSetDevice(k->device));
-    hipStream_t st = k->stream;
-    std::memcpy(k->h_a.p, rhs, k->nu * sizeof(double));
-    KHIP(hipMemcpyAsync(k->vin.p, k->h_a.p, k->nu * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipSetDevice(k->device));
+    stage_up(k, rhs, k->h_a, k->vin);
     solve_device(k, k->vin.p, k->vout.p);
-    KHIP(hipMemcpyAsync(k->h_b.p, k->vout.p, k->nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    KHIP(hipStreamSynchronize(st));
-    std::memcpy(x, k->h_b.p, k->nu * sizeof(double));
+    stage_down(k, k->vout.p, k->h_b, x);
   });
 }
 
 int pc_kkt_matvec(pc_kkt* k, int use_hess, const double* dvec, const double* x, double* y) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !dvec || !x || !y) throw std::runtime_error("null argument");
-    KHIP(hipSetDevice(k->device));
-    hipStream_t st = k->stream;
-    std::memcpy(k->h_a.p, dvec, k->nu * sizeof(double));
-    std::memcpy(k->h_b.p, x, k->nu * sizeof(double));
-    KHIP(hipMemcpyAsync(k->w_dvec.p, k->h_a.p, k->nu * sizeof(double), hipMemcpyHostToDevice, st));
-    KHIP(hipMemcpyAsync(k->vin.p, k->h_b.p, k->nu * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipSetDevice(k->device));
+    stage_up(k, dvec, k->h_a, k->w_dvec);
+    stage_up(k, x, k->h_b, k->vin);
     matvec_device<0>(k, use_hess, k->w_dvec.p, k->vin.p, nullptr, k->vout.p);
-    KHIP(hipMemcpyAsync(k->h_a.p, k->vout.p, k->nu * sizeof(double), hipMemcpyDeviceToHost, st));   // (queued behind the kernel that read dvec)
-    KHIP(hipStreamSynchronize(st));
-    std::memcpy(y, k->h_a.p, k->nu * sizeof(double));
+    stage_down(k, k->vout.p, k->h_a, y);   // (h_a again: the copy is queued behind the kernel that read dvec)
   });
 }
 
@@ -1758,7 +1574,7 @@ static double* solve_refined_device(pc_kkt* k, int use_hess, const double* d_dve
     auto norms = [&](const double* d_r, const double* d_t, double& sumsq, double& bad) {
       hipLaunchKernelGGL(kkt_norm_partial, dim3(nred), dim3(256), 0, st, d_r, d_t, k->w_part.p, nu);
       hipLaunchKernelGGL(kkt_norm_final, dim3(1), dim3(64), 0, st, k->w_part.p, nred, k->w_norm.p);
-      KHIP(hipMemcpyAsync(k->h_norm.p, k->w_norm.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_OK(hipMemcpyAsync(k->h_norm.p, k->w_norm.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
       kwait(st);
       sumsq = k->h_norm.p[0];
       bad = k->h_norm.p[1];
@@ -1776,13 +1592,13 @@ static double* solve_refined_device(pc_kkt* k, int use_hess, const double* d_dve
       hipLaunchKernelGGL(kkt_norm_final, dim3(1), dim3(64), 0, st, k->w_part.p + 2 * 256, nred, k->w_norm.p + 2);
       hipLaunchKernelGGL(kkt_norm_partial, dim3(nred), dim3(256), 0, st, res, sol, k->w_part.p, nu);
       hipLaunchKernelGGL(kkt_norm_final, dim3(1), dim3(64), 0, st, k->w_part.p, nred, k->w_norm.p);
-      KHIP(hipMemcpyAsync(k->h_norm.p, k->w_norm.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_OK(hipMemcpyAsync(k->h_norm.p, k->w_norm.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
       kwait(st);
       nres = k->h_norm.p[0];
       bad = k->h_norm.p[1];
       nrhs = k->h_norm.p[2];
     }
-    const double stop2 = k->resid_tol * k->resid_tol * nrhs;   // (NaN or 0 right-hand side: never true, the loop below decides)
+    const double stop2 = k->s.knobs.resid_tol * k->s.knobs.resid_tol * nrhs;   // (NaN or 0 right-hand side: never true, the loop below decides)
     for (int it = 0; it < max_steps; ++it) {
       if (nres <= stop2) break;                                 // already as accurate as a correction could make it matter
       solve_device(k, res, k->vout.p);
@@ -1805,34 +1621,28 @@ static double* solve_refined_device(pc_kkt* k, int use_hess, const double* d_dve
 
 int pc_kkt_solve_refined(pc_kkt* k, int use_hess, const double* dvec_true, const double* rhs, int max_steps, double* x,
                          int32_t* n_solves) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !dvec_true || !rhs || !x) throw std::runtime_error("null argument");
     if (!k->factored) throw std::runtime_error("pc_kkt_solve_refined before pc_kkt_factor");
-    KHIP(hipSetDevice(k->device));
-    hipStream_t st = k->stream;
-    const int64_t nu = k->nu;
-    std::memcpy(k->h_a.p, rhs, nu * sizeof(double));
-    std::memcpy(k->h_b.p, dvec_true, nu * sizeof(double));
-    KHIP(hipMemcpyAsync(k->w_rhs.p, k->h_a.p, nu * sizeof(double), hipMemcpyHostToDevice, st));
-    KHIP(hipMemcpyAsync(k->w_dvec.p, k->h_b.p, nu * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipSetDevice(k->device));
+    stage_up(k, rhs, k->h_a, k->w_rhs);
+    stage_up(k, dvec_true, k->h_b, k->w_dvec);
     int solves = 0;
     const double* sol = solve_refined_device(k, use_hess, k->w_dvec.p, k->w_rhs.p, max_steps, &solves);
-    KHIP(hipMemcpyAsync(k->h_b.p, sol, nu * sizeof(double), hipMemcpyDeviceToHost, st));
-    KHIP(hipStreamSynchronize(st));
-    std::memcpy(x, k->h_b.p, nu * sizeof(double));
+    stage_down(k, sol, k->h_b, x);
     if (n_solves) *n_solves = solves;
   });
 }
 
 int pc_kkt_solve_refined_device(pc_kkt* k, int use_hess, const double* d_dvec_true, const double* d_rhs, int max_steps,
                                 double* d_x, int32_t* n_solves) {
-  return guarded([&] {
+  return guarded(k_err, [&] {
     if (!k || !d_dvec_true || !d_rhs || !d_x) throw std::runtime_error("null argument");
     if (!k->factored) throw std::runtime_error("pc_kkt_solve_refined_device before a factorisation");
-    KHIP(hipSetDevice(k->device));
+    HIP_OK(hipSetDevice(k->device));
     int solves = 0;
     const double* sol = solve_refined_device(k, use_hess, d_dvec_true, d_rhs, max_steps, &solves);
-    KHIP(hipMemcpyAsync(d_x, sol, k->nu * sizeof(double), hipMemcpyDeviceToDevice, k->stream));
+    HIP_OK(hipMemcpyAsync(d_x, sol, k->nu * sizeof(double), hipMemcpyDeviceToDevice, k->stream));
     if (n_solves) *n_solves = solves;
   });
 }

@@ -178,7 +178,7 @@ void solution_costate(pc_solution* s, const double* d_lam, int n_orders, const i
 
 int solution_set_multipliers(pc_solution* s, const double* lam, int64_t n_lam, bool on_device, int n_orders, const int32_t* orders,
                              const double* tabA) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!s) throw std::runtime_error("null solution");
     require_device(s->h);
     pcs::check_multiplier_args(lam, n_lam, s->h->Q.num_c, tabA, s->h->w_J);
@@ -212,7 +212,7 @@ void solution_launch_sample_costate(pc_solution* s, int phase, const double* d_t
 
 int solution_create(pc_handle* h, const double* x, bool x_on_device, int n_orders, const int32_t* orders, const double* tabD,
                     const double* tabU, const double* tau, pc_solution** out) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     require_device(h);
     if (!x || !out) throw std::runtime_error("solution: null argument");
     *out = nullptr;
@@ -297,7 +297,7 @@ void pc_solution_destroy(pc_solution* sol) {
 }
 
 int pc_solution_sizes(pc_solution* sol, int phase, int32_t* N, int32_t* K, int32_t* NC, int32_t* n_y, int32_t* n_u) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     auto& S = solution_phase(sol, phase);
     if (N) *N = S.plan.N;
     if (K) *K = S.plan.K;
@@ -308,7 +308,7 @@ int pc_solution_sizes(pc_solution* sol, int phase, int32_t* N, int32_t* K, int32
 }
 
 int pc_solution_nodes(pc_solution* sol, int phase, double* time, double* y, double* dy, double* u) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     auto& S = solution_phase(sol, phase);
     const size_t N = (size_t)S.plan.N;
     solution_down(time, S.node_t, N);
@@ -319,7 +319,7 @@ int pc_solution_nodes(pc_solution* sol, int phase, double* time, double* y, doub
 }
 
 int pc_solution_coefficients(pc_solution* sol, int phase, double* dy_coef, double* u_coef) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     auto& S = solution_phase(sol, phase);
     solution_down(dy_coef, S.coef_dy, (size_t)S.plan.NC * S.NY);
     solution_down(u_coef, S.coef_u, (size_t)S.plan.NC * S.NU);
@@ -328,7 +328,7 @@ int pc_solution_coefficients(pc_solution* sol, int phase, double* dy_coef, doubl
 
 int pc_solution_sample(pc_solution* sol, int phase, const double* t, int64_t n_t, int flags, double* y, double* dy, double* u,
                        double* f) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!sol) throw std::runtime_error("null solution");
     pcs::check_sample_args((int)sol->ph.size(), phase, t, n_t, flags);
     auto& S = solution_phase(sol, phase);
@@ -351,7 +351,7 @@ int pc_solution_sample(pc_solution* sol, int phase, const double* t, int64_t n_t
 
 int pc_solution_sample_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_y, double* d_dy,
                               double* d_u, double* d_f) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!sol) throw std::runtime_error("null solution");
     pcs::check_sample_args((int)sol->ph.size(), phase, d_t, n_t, flags);
     (void)solution_phase(sol, phase);
@@ -370,7 +370,7 @@ int pc_solution_set_multipliers_device(pc_solution* sol, const double* d_lam, in
 }
 
 int pc_solution_costate_nodes(pc_solution* sol, int phase, double* p, double* H, double* nu) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     auto& S = solution_costate_phase(sol, phase);
     const size_t N = (size_t)S.plan.N;
     solution_down(p, S.node_p, N * S.NY);
@@ -380,14 +380,14 @@ int pc_solution_costate_nodes(pc_solution* sol, int phase, double* p, double* H,
 }
 
 int pc_solution_costate_coefficients(pc_solution* sol, int phase, double* p_coef) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     auto& S = solution_costate_phase(sol, phase);
     solution_down(p_coef, S.coef_p, (size_t)S.plan.NC * S.NY);
   });
 }
 
 int pc_solution_sample_costate(pc_solution* sol, int phase, const double* t, int64_t n_t, int flags, double* p, double* H) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!sol) throw std::runtime_error("null solution");
     pcs::check_sample_args((int)sol->ph.size(), phase, t, n_t, flags);
     auto& S = solution_costate_phase(sol, phase);
@@ -406,7 +406,7 @@ int pc_solution_sample_costate(pc_solution* sol, int phase, const double* t, int
 
 int pc_solution_sample_costate_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_p,
                                       double* d_H) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     if (!sol) throw std::runtime_error("null solution");
     pcs::check_sample_args((int)sol->ph.size(), phase, d_t, n_t, flags);
     auto& S = solution_costate_phase(sol, phase);
@@ -418,7 +418,7 @@ int pc_solution_sample_costate_device(pc_solution* sol, int phase, const double*
 int pc_solution_propagate(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
                           const double* atol, int64_t max_steps, double* y_arrive, int32_t* accepted, int32_t* rejected,
                           int32_t* seg_status) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     auto& S = solution_phase(sol, phase);
     if (!accepted || !rejected || !seg_status || (S.NY > 0 && !y_arrive)) throw std::runtime_error("propagate: null output");
     if (n_seg < 1 || n_seg > (int64_t)S.plan.N - 1) throw std::runtime_error("propagate: the number of segments must be in [1, N - 1]");
@@ -441,7 +441,7 @@ int pc_solution_propagate(pc_solution* sol, int phase, int64_t n_seg, const int3
 int pc_solution_propagate_device(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
                                  const double* atol, int64_t max_steps, double* d_y_arrive, int32_t* d_accepted,
                                  int32_t* d_rejected, int32_t* d_seg_status) {
-  return guarded([&] {
+  return guarded(g_err, [&] {
     (void)solution_phase(sol, phase);
     solution_launch_propagate(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, d_y_arrive, d_accepted, d_rejected,
                               d_seg_status);

@@ -570,6 +570,44 @@ class _KktInfo(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+def _descriptor(T: KktTables):
+    """``pc_kkt_desc`` of the tables, and the arrays it points into (to be kept alive as long as it is used)."""
+    d = _Desc()
+    keep = []
+    for k in SCALAR_FIELDS:
+        setattr(d, k, int(getattr(T, k)))
+    for k, counted in COUNT_FIELDS:
+        setattr(d, k, len(getattr(T, counted)))
+    for k, typ in ARRAY_FIELDS:
+        arr = np.ascontiguousarray(getattr(T, k), dtype=typ)
+        keep.append(arr if arr.size else np.zeros(1, dtype=typ))
+        setattr(d, k, _pointer(keep[-1]))
+    if T.chain_export is not None and np.any(T.chain_export):
+        keep.append(np.ascontiguousarray(T.chain_export, dtype=np.uint8))
+        d.chain_export = _pointer(keep[-1])
+    return d, keep
+
+
+def _info_dict(info) -> dict:
+    return {k: int(getattr(info, k)) for k, _ in _KktInfo._fields_ if k != "reserved"}
+
+
+def shape_info(tables: KktTables) -> dict:
+    """What ``GpuKkt.info`` of a fresh handle on ``tables`` would say, decided on the host alone (``pc_kkt_shape_info``:
+    no GPU is touched) under the current ``PYCOLLO_AMD_KKT_*`` environment; ``leaf_forward_stage`` is what the first
+    solve will pick.  Raises what ``pc_kkt_create`` would refuse."""
+    from .engine import load_library
+    lib = load_library()
+    lib.pc_kkt_last_error.restype = C.c_char_p
+    lib.pc_kkt_shape_info.argtypes = [C.POINTER(_Desc), C.POINTER(_KktInfo)]
+    d, keep = _descriptor(tables)
+    info = _KktInfo()
+    if not lib.pc_kkt_shape_info(C.byref(d), C.byref(info)):
+        raise RuntimeError("pc_kkt_shape_info failed: " + lib.pc_kkt_last_error().decode())
+    del keep
+    return _info_dict(info)
+
+
 class GpuKkt:
     """The factorisation object: ``pc_kkt_*`` bound to one engine's device-resident G~ / H~."""
 
@@ -603,19 +641,7 @@ class GpuKkt:
         lib.pc_kkt_export_panels.argtypes = [vp, vp]
         lib.pc_kkt_export_rhs.argtypes = [vp, vp]
         lib.pc_kkt_import_solution.argtypes = [vp, vp]
-        d = _Desc()
-        self._keep = []
-        for k in SCALAR_FIELDS:
-            setattr(d, k, int(getattr(T, k)))
-        for k, counted in COUNT_FIELDS:
-            setattr(d, k, len(getattr(T, counted)))
-        for k, typ in ARRAY_FIELDS:
-            arr = np.ascontiguousarray(getattr(T, k), dtype=typ)
-            self._keep.append(arr if arr.size else np.zeros(1, dtype=typ))
-            setattr(d, k, _pointer(self._keep[-1]))
-        if T.chain_export is not None and np.any(T.chain_export):
-            self._keep.append(np.ascontiguousarray(T.chain_export, dtype=np.uint8))
-            d.chain_export = _pointer(self._keep[-1])
+        d, self._keep = _descriptor(T)
         self._export_shapes = export_shapes(T)
         dg, dj, dh = vp(), vp(), vp()
         if not lib.pc_device_results(engine._h, C.byref(dg), C.byref(dj), C.byref(dh)):
@@ -641,7 +667,7 @@ class GpuKkt:
         leaf forward elimination (-1 before the first solve), the waves per leaf of the factorisation."""
         info = _KktInfo()
         self._check(self._lib.pc_kkt_get_info(self._h, C.byref(info)))
-        return {k: int(getattr(info, k)) for k, _ in _KktInfo._fields_ if k != "reserved"}
+        return _info_dict(info)
 
     def factor(self, dvec, use_hess=True):
         """Assemble from the engine's current device G~ / H~ and factorise; returns (n_pos, n_neg) pivots."""

@@ -139,3 +139,20 @@ def test_knob_sweeps_meet_the_reference(built, monkeypatch, name, kw):
             assert info["cr_top_waves"] == 2 and info["cr_top_levels"] <= base_info["cr_top_levels"]
         _agree(xs, base_x)
     case.close()
+
+
+@pytest.mark.parametrize("name,kw", [("hypersensitive", dict(K=8, order=3)), ("two_phase_transfer", {})])
+def test_info_after_a_solve_is_what_the_host_shape_says(built, monkeypatch, name, kw):
+    """``pc_kkt_shape_info`` decides on the host, without a device, what the handle then runs: field for field."""
+    from pycollo_amd.kkt import GpuKkt, shape_info
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    eng, _, x, lam, ineq, fixed, sc, dvec = kkt_case(name, kw, device=0)
+    eng.evaluate_resident(x, 1.0, lam)
+    k = GpuKkt(eng, ineq, fixed, sc)
+    k.factor(dvec)
+    k.solve(np.ones(k.nu))
+    assert k.info == shape_info(k.tables)
+    assert k.info["leaf_forward_stage"] >= 0
+    k.close()
+    eng.close()
