@@ -7,7 +7,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -18,6 +17,7 @@
 #include "pc_host.hpp"
 #include "pc_pattern.hpp"
 #include "pc_desc.hpp"
+#include "pc_eval_shape.hpp"
 #include "pc_deriv.hpp"
 #include "pc_solution_plan.hpp"
 
@@ -30,25 +30,15 @@ thread_local std::string g_err;
 
 void set_err(const std::string& s) { g_err = s; }
 
-using pcp::phase_nfs;
-using pcp::phase_lds_bytes;
-using pcp::phase_lds_out;
-using pcp::phase_max_tile_rows;
-
-struct PhaseDev {
+// a phase's share of the launch shape (pc_eval_shape.hpp) and what the device holds for it
+struct PhaseDev : pce::PhaseShape {
   DevBuf<int32_t> tile_k0, tile_n0, sec_s;
   DevBuf<double> sec_h, scal, partials, tab;
   DevBuf<int64_t> sec_E, hslot0, hslotN, hsum_slot;
   DevBuf<int32_t> hsum_local;
   DevBuf<unsigned long long> gran;   // resident tail: the per-tile partial sums as granules, [n_tiles][nred][2]
-  int32_t erec0 = 0;                 // resident tail: first record of this phase's edge-node Hessian entries
-  int uni_n = 0, spt = 0, lds_out = 0;
-  int lds_out4 = 0;                  // staging doubles per replica of a four-wave launch (one pass per state: pc::bulk NPASS)
-  int wpt = 1;                       // waves (replicas) per 64-node tile, see pc::bulk
   hipFunction_t fn = nullptr;
   hipFunction_t fn_res = nullptr;    // single-phase problems: bulk kernel with the resident tail as block 0
-  int lds_bytes = 0, n_tiles = 0, nfs = 0;
-  std::function<int(int)> lds_for;   // LDS bytes of this phase's workgroups with w staging regions
   int tile_begin = 0, tile_end = 0;  // launched tile range (whole phase unless sharded)
   double* partials_ext = nullptr;    // caller-owned partial-sum buffer (sharded exchange), else `partials`
   std::vector<double> scal_host;
@@ -103,17 +93,12 @@ __global__ void copy_runs_kernel(const double* __restrict__ src, double* __restr
 
 }  // namespace
 
-struct pc_handle {
+struct pc_handle : pce::Shape {   // the launch shape pc_create decided (pc_eval_shape.hpp), and what runs it
   pcp::Problem Q;
   int device = -1;
-  int TB = 64;
-  int TC = 64;   // nodes a tile may hold (<= TB)
-  bool two_wave = false;   // heavy model in the two-wave build: W = 2, tiles sized for four workgroups per CU
   bool scaling_set = false;
   double w_J = 1.0;
-  // quadrature
-  std::vector<double> qa, qw;
-  int32_t qa_off[PC_MAX_ORDER + 1], qw_off[PC_MAX_ORDER + 1];
+  std::vector<double> qa, qw;   // quadrature tables
   // device
   hipStream_t stream = nullptr;
   hipModule_t module = nullptr;
@@ -122,9 +107,6 @@ struct pc_handle {
   hipFunction_t tail_big_fn = nullptr;   // same kernel with the partial-sum loads of several strides in flight
   hipFunction_t bulk_all_fn = nullptr;   // multi-phase problems: every phase's bulk kernel in one launch
   DevBuf<char> d_phase_args;             // [n_phases] PcPhaseArgs read by pc_bulk_all
-  bool mixed = false;                    // some phase runs the mixed build: per-tile records pick the tile body
-  std::vector<PcTileRec> trec_all;       // records of every tile, phase after phase
-  std::vector<size_t> trec_base;         // [n_phases] first record of each phase in trec_all
   DevBuf<PcTileRec> d_trec;              // records of the launched tile ranges, in launch order
   std::vector<int> trec_first;           // [n_phases] first record of each phase in d_trec
   bool args_dirty = true;                // scaling / tile range / partials buffer changed since the last upload
@@ -133,15 +115,12 @@ struct pc_handle {
   std::vector<PcBulkArgs> host_bulk_args;   // per phase: lead scalars + argument block, kept filled between calls
   PcTailLaunch host_tail_launch;   // lead scalars + argument block of pc_tail, kept filled between calls
   bool host_args_dirty = true;
-  int wpt_all = 1, lds_all = 0;          // launch shape of pc_bulk_all
   std::vector<std::unique_ptr<PhaseDev>> pd;
   DevBuf<double> d_qa, d_pointV, d_pointr, d_Wend, d_norms;
-  // Host-pointer calls stage through ONE packed input block [x~ | lambda] and ONE packed output block
-  // [J | grad J non-zeros | c~ | G~ | H~] (pinned on the host, mirrored on the device): one copy up, one copy down.
+  // the packed input and output blocks (Shape::o_lam ...), pinned on the host and mirrored on the device: one copy
+  // up, one copy down
   DevBuf<double> d_in, d_out;
   PinBuf<double> h_in, h_out;
-  size_t o_lam = 0, in_total = 0;                              // offsets in doubles
-  size_t o_f = 0, o_gn = 0, o_c = 0, o_G = 0, o_H = 0, out_total = 0;
   // bit 0: the kernels read x~ / lambda straight from the pinned host block (no copy up);
   // bit 1: the kernels write their outputs straight into the pinned host block (no copy down)
   int host_mode = 0;
@@ -156,24 +135,17 @@ struct pc_handle {
   std::vector<double> h_pointV, h_pointr, h_Wend;   // host copies: travel by value in PcTailArgs
   // resident tail (pc_kernels.hpp, RES): one launch per evaluation, the tail runs as block 0 beside the tiles
   hipFunction_t bulk_all_res_fn = nullptr;   // multi-phase problems: pc_bulk_all with the resident tail
-  bool resident = true;                      // PYCOLLO_AMD_RESIDENT=0: always two launches (bulk, then pc_tail)
   DevBuf<unsigned long long> d_erec;         // granules of the edge-node Hessian entries endpoint terms are added to
   DevBuf<int64_t> d_rec_slot;                // [n_rec] H slot of every record (-1: site absent)
   DevBuf<int32_t> d_rec_term;                // [n_rec] endpoint Hessian entry added to the record, or -1
-  int32_t n_rec = 0;
   PinBuf<unsigned> h_timeout;                // host-visible: set by a tail whose granules never arrived
   uint32_t epoch = 0;                        // tag of the last resident launch's granules (never 0)
   int spin_us = 500;                         // host-pointer calls poll the stream this long before blocking (PYCOLLO_AMD_SPIN_US)
-  int tail_lds_bytes = 0, lds_nred = 0;
-  bool heavy_point = false;                  // the endpoint block is worth one tail workgroup per part when tiles are single waves
-  int tail_blocks_env = 0;
   DevBuf<unsigned long long> d_hb_gran;      // endpoint Hessian terms handed between the tail's workgroups
   PinBuf<double> h_norms;
   std::vector<double> V_ocp, r_ocp, W_ocp;
   int n_launches = 0;
   int last_launch = 0;                       // pc_info.last_launch: the builds the last evaluation launched
-  int lds_max = 0;
-  int lds_limit = 64 * 1024;  // dynamic LDS a workgroup may request (queried from the device)
   // derivative check (pc_deriv.hpp, pc_deriv_check.hpp): colouring plan and scratch, built on first use
   mutable std::shared_ptr<pcd::Plan> deriv_plan;
   std::shared_ptr<pc_deriv_dev> deriv_dev;
@@ -328,6 +300,11 @@ void launch_block(hipFunction_t fn, unsigned grid, unsigned block, size_t lds, h
   HIP_OK(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, (unsigned)lds, stream, nullptr, cfg));
 }
 
+// the code object has the kernel that runs the tail beside the tiles, and the handle may use it
+bool has_resident_kernel(const pc_handle* h) {
+  return h->resident && (h->Q.ph.size() > 1 ? h->bulk_all_res_fn != nullptr : h->pd[0]->fn_res != nullptr);
+}
+
 void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_c, double* d_G, double* d_H,
                 double* d_fobj, double* d_gradnz, int flags, hipStream_t st, double sigma, bool bulk = true,
                 bool tail = true) {
@@ -335,7 +312,7 @@ void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_
   // One launch per evaluation when every phase runs whole on this device: the tail is block 0 of the bulk launch and
   // receives the tiles' partial sums as granules (pc_kernels.hpp, RES).  A rank of the section-sharded evaluation,
   // whose sums travel through the all-gather first, and the bulk-only / tail-only calls take two launches.
-  bool res = bulk && tail && h->resident && (Q.ph.size() > 1 ? h->bulk_all_res_fn != nullptr : h->pd[0]->fn_res != nullptr);
+  bool res = bulk && tail && has_resident_kernel(h);
   for (size_t ip = 0; res && ip < Q.ph.size(); ++ip) {
     auto& D = *h->pd[ip];
     res = D.tile_begin == 0 && D.tile_end == D.n_tiles && !D.partials_ext;
@@ -402,7 +379,7 @@ void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_
     for (size_t ip = Q.ph.size(); ip <= PC_MAX_PHASES; ++ip) m.first_block[ip] = nb;
     if (res) {
       const int bt = h->TB * h->wpt_all;
-      const int ntb = h->tail_blocks_env > 0 ? h->tail_blocks_env : ((h->heavy_point && bt < 256) ? 4 : 1);
+      const int ntb = h->tail_blocks_all;
       m.tail_blocks = ntb;
       mr.t = h->host_tail_launch.t;
       patch_tail(mr.t, bt);
@@ -446,7 +423,7 @@ void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_
       BulkRes br;
       br.ba = ba;
       br.t = h->host_tail_launch.t;
-      const int ntb = h->tail_blocks_env > 0 ? h->tail_blocks_env : ((h->heavy_point && a.block_threads < 256) ? 4 : 1);
+      const int ntb = h->tail_blocks;
       br.ba.lead.wa |= ntb << 28;
       patch_tail(br.t, a.block_threads);
       br.t.n_tail_blocks = ntb;
@@ -469,10 +446,7 @@ void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_
   tl.lead = PcTailLead{t.x, t.ph[0].partials, t.ph[0].scal, t.ph[0].x_off, t.ph[0].n_tiles, t.ph[0].N, t.flags, t.block_threads};
   size_t sz = sizeof(tl);
   void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &tl, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  // more than four strides of partial sums per lane in some phase: the build that overlaps their loads
-  int max_tiles = 0;
-  for (size_t ip = 0; ip < Q.ph.size(); ++ip) max_tiles = std::max(max_tiles, (int)t.ph[ip].n_tiles);
-  hipFunction_t fn = (h->tail_big_fn && max_tiles > 4 * PC_TAIL_THREADS) ? h->tail_big_fn : h->tail_fn;
+  hipFunction_t fn = (h->tail_big_fn && h->tail_big) ? h->tail_big_fn : h->tail_fn;
   HIP_OK(hipModuleLaunchKernel(fn, 1, 1, 1, PC_TAIL_THREADS, 1, 1, h->tail_lds_bytes, st, nullptr, cfg));
   h->last_launch = last | (fn == h->tail_big_fn ? 2 : 0) | ((PC_TAIL_THREADS / 64) << 8);
 }
@@ -611,6 +585,37 @@ hipError_t find_fn(pc_handle* h, hipFunction_t* fn, const char* name) {
   return e;
 }
 
+// The one reader of the launch shape's knobs (pc_eval_shape.hpp::Knobs): the environment, and the LDS a workgroup of
+// `device` may request.
+pce::Knobs read_knobs(int device) {
+  pce::Knobs kn;
+  auto env_int = [](const char* name, auto& dst) {
+    if (const char* env = std::getenv(name)) dst = std::atoi(env);
+  };
+  auto env_i64 = [](const char* name, int64_t& dst) {
+    if (const char* env = std::getenv(name)) dst = std::atoll(env);
+  };
+  auto env_flag = [](const char* name, bool& dst) {
+    if (const char* env = std::getenv(name)) dst = std::atoi(env) != 0;
+  };
+  env_int("PYCOLLO_AMD_TB", kn.tb);
+  env_int("PYCOLLO_AMD_WPT", kn.wpt);
+  env_int("PYCOLLO_AMD_TILE_NODES", kn.tile_nodes);
+  env_flag("PYCOLLO_AMD_TWO_WAVE", kn.two_wave);
+  env_i64("PYCOLLO_AMD_TWO_WAVE_MAX_TILES", kn.two_wave_max_tiles);
+  env_i64("PYCOLLO_AMD_TWO_WAVE_TILES", kn.two_wave_tiles);
+  env_i64("PYCOLLO_AMD_TWO_WAVE_MAX_WAVES", kn.two_wave_max_waves);
+  env_int("PYCOLLO_AMD_MIX_MIN_RUN_ROWS", kn.mix_min_run_rows);
+  env_int("PYCOLLO_AMD_MIX_CAP_ROWS", kn.mix_cap_rows);
+  env_flag("PYCOLLO_AMD_RESIDENT", kn.resident);
+  env_int("PYCOLLO_AMD_TAIL_BLOCKS", kn.tail_blocks);
+  env_flag("PYCOLLO_AMD_MERGE", kn.merge);
+  int v = 0;
+  if (device >= 0 && hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && v > 0)
+    kn.lds_limit = v;
+  return kn;
+}
+
 }  // namespace
 
 extern "C" {
@@ -626,353 +631,24 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
     h.reset(new pc_handle());
     auto& Q = h->Q;
     pcp::from_desc(*d, Q);   // pc_desc.hpp: plain C++, also compiled (with sanitizers) by the CPU test harness
-    // quadrature tables
-    for (int i = 0; i <= PC_MAX_ORDER; ++i) h->qa_off[i] = h->qw_off[i] = -1;
-    {
-      size_t oa = 0, ow = 0;
-      for (int i = 0; i < d->n_orders; ++i) {
-        const int n = d->orders[i];
-        if (n < 2 || n > PC_MAX_ORDER) throw std::runtime_error("quadrature order outside [2, 20]");
-        h->qa_off[n] = (int32_t)oa;
-        h->qw_off[n] = (int32_t)ow;
-        oa += (size_t)(n - 1) * n;
-        ow += n;
-      }
-      h->qa.assign(d->quad_A, d->quad_A + oa);
-      h->qw.assign(d->quad_w, d->quad_w + ow);
+    const pce::Knobs kn = read_knobs(d->device);
+    static_cast<pce::Shape&>(*h) = pce::build_shape(*d, Q, kn);   // pc_eval_shape.hpp: plain C++, tested on the CPU
+    h->pd.resize(Q.ph.size());
+    for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
+      h->pd[ip].reset(new PhaseDev());
+      static_cast<pce::PhaseShape&>(*h->pd[ip]) = h->ph[ip];
+      h->pd[ip]->tile_end = h->ph[ip].n_tiles;
     }
-    // threads per block
-    int64_t Nmax = 0;
-    for (int ip = 0; ip < d->n_phases; ++ip) {
-      int64_t N = 1;
-      for (int k = 0; k < d->phases[ip].K; ++k) N += d->phases[ip].n_k[k] - 1;
-      Nmax = std::max(Nmax, N);
-    }
-    int TB = d->threads_per_block;
-    if (const char* env = std::getenv("PYCOLLO_AMD_TB")) TB = std::atoi(env);
-    if (d->device >= 0) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, d->device) == hipSuccess && v > 0)
-        h->lds_limit = v;
-    }
-    const bool auto_tb = (TB == 0);
-    if (auto_tb) {
-      TB = Nmax >= 262144 ? 256 : (Nmax >= 65536 ? 128 : 64);
-      // a one-state model has so little per node that the widest workgroup pays much earlier (hypersensitive, TB =
-      // 64 / 128 / 256: 20 k nodes 5.11 / 4.94-5.21 / 5.0-5.2 us, 30 k 5.46 / 5.41 / 5.18, 50 k 6.67 / 5.81 / 5.70,
-      // 65 k 8.92 / 6.76 / 5.90, 150 k 14.5 / 9.05 / 8.27, 250 k 22.1 / 12.1 / 9.97)
-      bool one_state = true;
-      for (int ip = 0; ip < d->n_phases; ++ip) one_state = one_state && d->phases[ip].n_y == 1 && d->phases[ip].eval_ops <= 4000;
-      if (one_state && Nmax >= 25000) TB = 256;
-    }
-    if (TB != 64 && TB != 128 && TB != 256) throw std::runtime_error("threads_per_block must be 64, 128 or 256");
-    for (auto& P : Q.ph) pcp::finalize_phase_tables(P, Q.n_s);
-    const int qa_n = (int)h->qa.size(), qw_n = (int)h->qw.size();
-    // bytes of LDS a workgroup of W waves needs when tiles hold at most `tc` nodes (worst phase; before the tiles exist:
-    // a tile of tc nodes has at most tc - 1 defect rows per state)
-    auto lds_need = [&](int tb, int tc, int W) {
-      int mx = 0;
-      for (auto& P : Q.ph)
-        mx = std::max(mx, phase_lds_bytes(P, W > 1 ? 64 : tb, qa_n, qw_n, W * phase_lds_out(P, tc - 1, tc), P.compiled_order == 0));
-      return mx;
-    };
-    if (auto_tb)   // largest tile whose staging fits the 64 KiB of dynamic LDS a module kernel may request
-      while (TB > 64 && lds_need(TB, TB, 1) > h->lds_limit) TB /= 2;
-    h->TB = TB;
-    // Tile capacity in nodes (<= TB): a tile smaller than its workgroup leaves lanes idle but shortens every
-    // wave's store phase and puts more waves on the chip -- what a problem with far fewer tiles than SIMDs wants.
-    int TC = TB, max_nk = 2;
-    for (auto& P : Q.ph)
-      for (int k = 0; k < P.K; ++k) max_nk = std::max(max_nk, P.n_k[k]);
-    // The two-wave build of a heavy model (codegen: pc_bulk_all_r_w2 / pc_bulk_p<i>_r_w2, <= 256 registers): two waves
-    // share every 64-node tile, each with its own staging region, and a SIMD holds two of them -- if the CU's 160 KiB of
-    // LDS hold four tiles.  The tile capacity is the largest that allows it (Delta III, order 5: 60 rows of 40 doubles per
-    // replica; 4 x 12.5 k nodes 30.6 -> 23.2 us).  PYCOLLO_AMD_TWO_WAVE=0 turns the mode off; an explicit
-    // PYCOLLO_AMD_WPT / PYCOLLO_AMD_TILE_NODES leaves the choice to the caller.
-    for (auto& P : Q.ph) h->mixed = h->mixed || !P.spec_orders.empty();
-    h->two_wave = d->two_wave_occupancy >= 2 && TB == 64 && !std::getenv("PYCOLLO_AMD_WPT") &&
-                  !std::getenv("PYCOLLO_AMD_TILE_NODES");
-    if (const char* env = std::getenv("PYCOLLO_AMD_TWO_WAVE")) h->two_wave = h->two_wave && std::atoi(env) != 0;
-    {   // with few tiles (a rank's share of a sharded mesh, a coarse mesh) four waves per tile serve better: one wave
-        // per SIMD either way, and the shorter one wins
-      int64_t tiles64 = 0;
-      for (auto& P : Q.ph) {
-        int64_t N = 1;
-        for (int k = 0; k < P.K; ++k) N += P.n_k[k] - 1;
-        tiles64 += (N + 62) / 63;
-        h->two_wave = h->two_wave && P.n_y >= 2;
-      }
-      // ... and with many more tiles than the chip holds at once the replicas' second evaluation of the node functions
-      // buys nothing: the (split, register-capped) one-wave-per-tile kernel already runs two waves per SIMD
-      int64_t max_tiles = 1 << 30;
-      if (const char* env = std::getenv("PYCOLLO_AMD_TWO_WAVE_MAX_TILES")) max_tiles = std::atoll(env);
-      h->two_wave = h->two_wave && tiles64 > 400 && tiles64 <= max_tiles;
-    }
-    constexpr int kQuarterCu = 30 * 1280;
-    // A two-wave launch is one generation of waves and lasts one wave's life, which grows with the tile's rows (its
-    // share of the flush): the tile capacity is the one that cuts the mesh into about 896 tiles (3.5 workgroups per CU,
-    // 1 792 of the chip's 2 048 wave slots) when that is smaller than what the LDS allows.  Measured on one box, Delta III
-    // 4 x 12.5 k nodes, tiles / us: order 4  796 / 25.8, 928 / 22.3, 984 / 22.4;  order 5  896 / 23.2, 964 / 26.0;  order 6
-    // 836 / 32.1, 912 / 29.3, 1000 / 28.8;  order 7  836 / 31.4, 928 / 27.7;  order 8  796 / 35.7, 896 / 32.0, 1020 / 33.6
-    // (profiles/r04_two_wave_tiles.txt).  PYCOLLO_AMD_TWO_WAVE_TILES overrides the target (0: the largest tile the LDS allows).
-    auto fill_tc = [&](int tc_max) {
-      int64_t want = 896;
-      if (const char* env = std::getenv("PYCOLLO_AMD_TWO_WAVE_TILES")) want = std::atoll(env);
-      if (want <= 0) return tc_max;
-      int64_t rows = 0;
-      for (auto& P : Q.ph)
-        for (int k = 0; k < P.K; ++k) rows += P.n_k[k] - 1;
-      const int per = (int)((rows + want - 1) / want);
-      return std::max(std::max(max_nk, 24), std::min(tc_max, per + 1));
-    };
-    if (h->mixed) {
-      // Mixed build: tiles are cut per order (pc_pattern.hpp::build_tiles_mixed) under row caps that keep a workgroup's
-      // LDS inside the budget -- a quarter CU for the two-wave build (below), else what a workgroup may request -- and
-      // the two-wave build is kept when every wave of the launch is then resident at once, as for a uniform mesh.
-      if (const char* env = std::getenv("PYCOLLO_AMD_MIX_MIN_RUN_ROWS"))
-        for (auto& P : Q.ph) P.min_run_rows = std::max(1, std::atoi(env));
-      auto cut = [&](int W, int budget) {
-        int64_t tiles = 0;
-        for (auto& P : Q.ph) {
-          if (!P.spec_orders.empty()) {
-            pcp::phase_set_caps(P, W > 1 ? 64 : TB, W, qa_n, qw_n, budget);
-            // A launch is one generation of waves and lasts as long as its slowest one: a tile of several orders runs
-            // the any-order body, which takes about twice as long per row as an order-specialised one -- such tiles are
-            // kept to half the rows so that they finish with the others (measured: with 63-row any-order tiles among
-            // 835 order-pure ones the mixed build ran no faster than the any-order kernel alone, 51.3 / 50.6 us)
-            int mix_rows = 32;
-            if (const char* env = std::getenv("PYCOLLO_AMD_MIX_CAP_ROWS")) mix_rows = std::max(8, std::atoi(env));
-            P.mix_cap_rows = std::min(P.mix_cap_rows, mix_rows);
-          }
-          pcp::build_tiles(P, TC);
-          tiles += (int64_t)P.tile_k0.size() - 1;
-        }
-        return tiles;
-      };
-      if (h->two_wave) {
-        // (phases of a single order inside a mixed problem: one tile capacity for them, as below)
-        int tc = 64;
-        auto need_uniform = [&](int t) {
-          int mx = 0;
-          for (auto& P : Q.ph)
-            if (P.spec_orders.empty())
-              mx = std::max(mx, phase_lds_bytes(P, 64, qa_n, qw_n, 2 * phase_lds_out(P, t - 1, t), P.compiled_order == 0));
-          return mx;
-        };
-        while (tc > std::max(max_nk, 32) && need_uniform(tc) > kQuarterCu) --tc;
-        int64_t max_waves = 2048;   // every wave of the launch resident at once (two per SIMD)
-        if (const char* env = std::getenv("PYCOLLO_AMD_TWO_WAVE_MAX_WAVES")) max_waves = std::atoll(env);
-        // the smallest tile capacity from the chip-filling one upwards whose cut keeps every wave resident
-        bool fits = false, fixed = false;
-        for (auto& P : Q.ph) fixed = fixed || !P.fixed_tile_k0.empty();
-        if (fixed) {   // the caller's tiles (a rank-local handle): two waves per tile when its actual tiles allow it
-          TC = 64;
-          const int64_t tiles = cut(2, kQuarterCu);
-          int need = 0;
-          for (auto& P : Q.ph)
-            if (!P.spec_orders.empty()) {
-              bool ap = false, ag = false;
-              const int out = 2 * phase_lds_out_tiles(P, &ap, &ag);
-              if (ag) need = std::max(need, phase_lds_bytes(P, 64, qa_n, qw_n, out, true, true));
-              if (ap) need = std::max(need, phase_lds_bytes(P, 64, qa_n, qw_n, out, false, true));
-            }
-          fits = need <= kQuarterCu && need_uniform(64) <= kQuarterCu && 2 * tiles <= max_waves;
-        }
-        for (int t = std::min(tc, fill_tc(tc)); !fixed && t <= tc && !fits; ++t) {
-          TC = t;
-          fits = need_uniform(t) <= kQuarterCu && 2 * cut(2, kQuarterCu) <= max_waves;
-        }
-        if (!fits) {
-          h->two_wave = false;
-          TC = TB;
-        }
-      }
-      if (!h->two_wave) cut(1, h->lds_limit);
-    } else if (h->two_wave) {
-      // four workgroups per CU: a quarter of the 160 KiB less two allocation granules of 1280 B -- measured, Delta III
-      // 4 x 12.5 k nodes: 37 272 B per workgroup 23.2 us, 39 832 B (nominally still a quarter) 26.8 us
-      int tc = 64;
-      while (tc > std::max(max_nk, 32) && lds_need(64, tc, 2) > kQuarterCu) --tc;
-      // ... and every wave of the launch resident at once (2048 wave slots at two per SIMD): with smaller tiles than
-      // that allows, the one-wave-per-tile kernel -- itself two waves per SIMD -- is as fast or faster (Delta III order 6:
-      // 1160 tiles of 45 nodes x 2 waves 34.0 us, 872 tiles x 1 wave 32.2 us; 4 x 25 k nodes, order 5: 42.7 / 42.2 us)
-      auto tiles_at = [&](int t) {
-        int64_t tiles_tc = 0;
-        for (auto& P : Q.ph) {
-          int64_t N = 1, nmax = 2;
-          for (int k = 0; k < P.K; ++k) { N += P.n_k[k] - 1; nmax = std::max<int64_t>(nmax, P.n_k[k]); }
-          const int64_t per_tile = std::max<int64_t>(1, ((t - 1) / (nmax - 1)) * (nmax - 1));
-          tiles_tc += (N - 1 + per_tile - 1) / per_tile;
-        }
-        return tiles_tc;
-      };
-      bool fits = false;
-      if (lds_need(64, tc, 2) <= kQuarterCu)
-        for (int t = std::min(tc, fill_tc(tc)); t <= tc && !fits; ++t)
-          if (2 * tiles_at(t) <= 2048) { TC = t; fits = true; }
-      if (!fits) h->two_wave = false;
-    }
-    if (const char* env = std::getenv("PYCOLLO_AMD_TILE_NODES")) {
-      const int v = std::atoi(env);
-      if (v >= max_nk && v <= TB) TC = v;
-    }
-    h->TC = TC;
-    if (d->plan_only) {   // the tiling alone (a rank of the section-sharded evaluation asks for its range, sharding.py)
-      pcp::build_all(Q, TC, true);
-      h->device = -1;
-      h->pd.resize(Q.ph.size());
-      for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
-        h->pd[ip].reset(new PhaseDev());
-        h->pd[ip]->n_tiles = (int)Q.ph[ip].tile_k0.size() - 1;
-      }
-      return;
-    }
-    pcp::build_all(Q, TC);
-    if (h->mixed) {   // one record per tile: which body runs it and where it sits in the mesh
-      for (auto& P : Q.ph)
-        for (int k = 0; k < P.K; ++k)
-          if (h->qa_off[P.n_k[k]] < 0) throw std::runtime_error("no quadrature table for a section order in use");
-      h->trec_base.assign(Q.ph.size(), 0);
-      for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
-        auto& P = Q.ph[ip];
-        h->trec_base[ip] = h->trec_all.size();
-        for (size_t t = 0; t + 1 < P.tile_k0.size(); ++t) {
-          PcTileRec r{};
-          const int k0 = P.tile_k0[t];
-          r.phase = (int32_t)ip;
-          r.tile = (int32_t)t;
-          r.order = t < P.tile_order.size() ? P.tile_order[t] : 0;
-          r.k0 = k0;
-          r.nsec = P.tile_k0[t + 1] - k0;
-          r.n0 = P.sec_s[k0];
-          r.nprev = k0 > 0 ? P.n_k[k0 - 1] : 0;
-          r.qa_prev = r.nprev ? h->qa_off[r.nprev] : 0;
-          r.E0 = P.sec_E[k0];
-          r.w_prev = r.nprev ? h->qw[h->qw_off[r.nprev] + r.nprev - 1] : 0.0;
-          h->trec_all.push_back(r);
-        }
-      }
-    }
-    if (Q.point_x.size() > PC_MAX_POINT || Q.n_b > PC_MAX_ENDPOINT_ROWS)
-      throw std::runtime_error("too many endpoint variables / endpoint constraints for the tail kernel's argument block");
-    if (Q.tail_owned.size() > PC_TAIL_OWNED_MAX)
-      throw std::runtime_error("too many Hessian entries owned by the tail kernel (static parameters / endpoint terms)");
-    for (auto& P : Q.ph)
-      for (int k = 0; k < P.K; ++k)
-        if (h->qa_off[P.n_k[k]] < 0) throw std::runtime_error("no quadrature table for a section order in use");
+    h->ph = {};   // (the phases' shapes live in pd from here on, once)
+    if (d->plan_only) return;   // the tiling alone (a rank of the section-sharded evaluation asks for its range, sharding.py)
+    h->qa.assign(d->quad_A, d->quad_A + h->qa_n);
+    h->qw.assign(d->quad_w, d->quad_w + h->qw_n);
     h->device = d->device;
     h->V_ocp.assign(Q.num_ocp_x, 1.0);
     h->r_ocp.assign(Q.num_ocp_x, 0.0);
     h->W_ocp.assign(Q.num_ocp_c, 1.0);
-    if (const char* env = std::getenv("PYCOLLO_AMD_RESIDENT")) h->resident = std::atoi(env) != 0;
     if (const char* env = std::getenv("PYCOLLO_AMD_SPIN_US")) h->spin_us = std::atoi(env);
-    // the endpoint block is generated in four parts, one per wave of a 256-thread tail; a small block is not worth
-    // the three extra waves every tile's workgroup then carries (they exit at their first instruction)
-    h->heavy_point = Q.point_x.size() + (size_t)Q.n_b + Q.pthess_row.size() > 16;
-    if (const char* env = std::getenv("PYCOLLO_AMD_TAIL_BLOCKS")) h->tail_blocks_env = std::min(4, std::max(0, std::atoi(env)));
-    // the tail's LDS carve (pc::tail_lds): acc | part | sum | xb | lb | hold | hb
-    for (auto& P : Q.ph) h->lds_nred = std::max(h->lds_nred, P.nred);
-    h->tail_lds_bytes = 8 * (int)(Q.tail_owned.size() + 17 * (size_t)h->lds_nred + Q.point_x.size() + (size_t)Q.n_b +
-                                  2 * Q.pthess_row.size() + 2);
-    h->pd.resize(Q.ph.size());
-    for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
-      h->pd[ip].reset(new PhaseDev());
-      auto& P = Q.ph[ip];
-      auto& D = *h->pd[ip];
-      D.n_tiles = (int)P.tile_k0.size() - 1;
-      D.tile_begin = 0;
-      D.tile_end = D.n_tiles;
-      const int nfs = phase_nfs(P);
-      D.nfs = nfs;
-      const bool mesh_tables = P.compiled_order == 0;
-      // uniform section order: index arithmetic replaces the section tables
-      bool same = true;
-      for (int k = 0; k < P.K; ++k) same = same && P.n_k[k] == P.n_k[0];
-      same = same && P.fixed_tile_k0.empty();   // (a caller's tile table is read from the tables, never computed from the tile index)
-      D.uni_n = same ? P.n_k[0] : 0;
-      D.spt = same ? (TC - 1) / (P.n_k[0] - 1) : 0;
-      if (same && P.tile_k0.size() > 1 && P.tile_k0[1] != std::min(D.spt, P.K))
-        throw std::runtime_error("internal error: uniform tiling mismatch");
-      D.lds_out = phase_lds_out(P, phase_max_tile_rows(P), std::min(TC, phase_max_tile_rows(P) + 1));   // the largest tile's runs
-      bool any_pure = false, any_generic = false;
-      D.lds_out4 = phase_lds_out(P, phase_max_tile_rows(P), std::min(TC, phase_max_tile_rows(P) + 1), false);
-      if (!P.spec_orders.empty()) {   // every row with its own order
-        D.lds_out = phase_lds_out_tiles(P, &any_pure, &any_generic);
-        D.lds_out4 = phase_lds_out_tiles(P, nullptr, nullptr, false);
-      }
-      // LDS of the phase's workgroups with w staging regions: the larger of the tile bodies the phase's tiles run
-      D.lds_for = [&P, &D, TB, qa_n, qw_n, mesh_tables, any_pure, any_generic](int w) {
-        const int out = (w == 4 ? D.lds_out4 : D.lds_out) * w;
-        if (P.spec_orders.empty()) return phase_lds_bytes(P, TB, qa_n, qw_n, out, mesh_tables);
-        int b = 0;
-        if (any_generic) b = std::max(b, phase_lds_bytes(P, TB, qa_n, qw_n, out, true, true));
-        if (any_pure) b = std::max(b, phase_lds_bytes(P, TB, qa_n, qw_n, out, false, true));
-        return b;
-      };
-      // Few tiles and several states: W waves share a tile and split its output runs, so that the chip's 1024
-      // SIMDs each hold a wave (or two) instead of a fraction of them holding one long-running wave.  Beyond that
-      // the replicas only add redundant node evaluations (measured on 64-node tiles, W = 1 / 2 / 4: shuttle
-      // 381 tiles 22.7 / 19.2 / 17.6 us, 953 tiles 25.2 / 23.3 / 31.3 us, 2858 tiles 54 / 60 / 81 us).
-      D.wpt = 1;
-      if (TB == 64) {
-        // (one state: W = 2 measured no faster, 5.58 vs 5.49 us.  A heavy model -- Delta III, ~10k operations --
-        //  loses at 834 tiles, 358 / 410 / 522 us: every sharing wave re-evaluates the node functions)
-        const bool heavy = P.eval_ops > 4000;
-        if (P.n_y >= 2 && D.n_tiles <= (heavy ? 512 : 1024)) D.wpt = 2;
-        if (P.n_y >= 3 && D.n_tiles <= 400) D.wpt = 4;
-        // One state, one launch per evaluation: the last tile's store phase is what the launch waits for once the tail
-        // runs beside the tiles, and four waves get a tile's runs out sooner than one (hypersensitive, W = 1 / 2 / 4:
-        // 42 tiles 4.69 / 4.34 / 4.25 us, 167 tiles 4.78-4.99 / 4.59-4.87 / 4.46-4.69, 334 tiles 5.94 / 5.00 / 4.94,
-        // 500 tiles 5.92 / 5.29 / 5.44; with a separate tail launch W = 2 measured no gain, 5.58 vs 5.49 us)
-        if (P.n_y == 1 && !heavy && h->resident) D.wpt = D.n_tiles <= 400 ? 4 : (D.n_tiles <= 1024 ? 2 : 1);
-        if (const char* env = std::getenv("PYCOLLO_AMD_WPT")) {
-          const int v = std::atoi(env);
-          if (v == 1 || v == 2 || v == 4) D.wpt = v;
-        }
-        if (h->two_wave) D.wpt = 2;
-        while (D.wpt > 1 && D.lds_for(D.wpt) > h->lds_limit) D.wpt /= 2;
-      }
-      D.lds_bytes = D.lds_for(D.wpt);
-      h->lds_max = std::max(h->lds_max, D.lds_bytes);
-      if (D.lds_bytes > h->lds_limit)
-        throw std::runtime_error("tile needs more dynamic LDS than a workgroup may request; use a smaller "
-                                 "threads_per_block");
-      if ((int)P.goff.size() > PC_MAX_GOFF || (int)P.hoff.size() > PC_MAX_HOFF)
-        throw std::runtime_error("too many variables/constraints per phase for the kernel argument block");
-    }
     h->n_launches = (int)Q.ph.size() + 1;   // refined after the module is loaded (resident tail: one launch)
-    // launch shape of the all-phases kernel: the phases share one workgroup size, chosen from the total tile count
-    if (Q.ph.size() > 1) {
-      int total = 0, min_ny = 1 << 30;
-      bool heavy = false;
-      for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
-        total += h->pd[ip]->n_tiles;
-        min_ny = std::min(min_ny, Q.ph[ip].n_y);
-        heavy = heavy || Q.ph[ip].eval_ops > 4000;
-      }
-      h->wpt_all = 1;
-      auto lds_for = [&](int w) {
-        int mx = 0;
-        for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
-          auto& P = Q.ph[ip];
-          auto& D = *h->pd[ip];
-          (void)P;
-          mx = std::max(mx, D.lds_for(w));
-        }
-        return mx;
-      };
-      if (TB == 64) {
-        if (min_ny >= 2 && total <= (heavy ? 512 : 1024)) h->wpt_all = 2;
-        if (min_ny >= 3 && total <= 400) h->wpt_all = 4;
-        if (const char* env = std::getenv("PYCOLLO_AMD_WPT")) {
-          const int v = std::atoi(env);
-          if (v == 1 || v == 2 || v == 4) h->wpt_all = v;
-        }
-        if (h->two_wave) h->wpt_all = 2;
-        while (h->wpt_all > 1 && lds_for(h->wpt_all) > h->lds_limit) h->wpt_all /= 2;
-      }
-      h->lds_all = lds_for(h->wpt_all);
-    }
     if (h->device < 0) return;  // structure-only handle
 
     // ---- device side ----------------------------------------------------------------------------
@@ -1001,9 +677,7 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
     if (find_fn(h.get(), &h->tail_big_fn, (std::string(d->tail_kernel) + "_big").c_str()) != hipSuccess)
       h->tail_big_fn = nullptr;
     if (Q.ph.size() > 1) {
-      bool merge = true;
-      if (const char* env = std::getenv("PYCOLLO_AMD_MERGE")) merge = std::atoi(env) != 0;
-      if (!merge || find_fn(h.get(), &h->bulk_all_fn, "pc_bulk_all") != hipSuccess) h->bulk_all_fn = nullptr;
+      if (!kn.merge || find_fn(h.get(), &h->bulk_all_fn, "pc_bulk_all") != hipSuccess) h->bulk_all_fn = nullptr;
       if (h->bulk_all_fn) {
         h->d_phase_args.alloc(Q.ph.size() * sizeof(PcPhaseArgs));
         h->n_launches = 2;
@@ -1051,46 +725,9 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
       D.partials.alloc((size_t)std::max(1, P.nred) * D.n_tiles);
       D.gran.upload(std::vector<unsigned long long>((size_t)2 * std::max(1, P.nred) * D.n_tiles, 0ull));   // tag 0: never written
     }
-    {
-      // Resident tail: a Hessian entry of an edge node 0 / N-1 on which an endpoint term lands reaches the tail
-      // workgroup as a record (two granules); the tail adds the term and stores the entry.  Records are numbered per
-      // phase, node 0 then node N-1, in the kernels' site order (z-z entries, t strips, s strips) -- the order the
-      // generated kernels rank their compile-time flags in (codegen.edge_flags, S<M>::erank).
-      std::map<int64_t, int32_t> term_of_slot;   // slot -> endpoint entry
-      for (size_t e = 0; e < Q.pt_hslot.size(); ++e)
-        if (Q.pt_hlocal[e] < 0) term_of_slot.emplace(Q.pt_hslot[e], (int32_t)e);
-      std::vector<int64_t> rec_slot;
-      std::vector<int32_t> rec_term;
-      for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
-        auto& P = Q.ph[ip];
-        const int NZ = P.n_z, NS = P.n_w, NHZZ = (int)P.hslot0.size(), NE = NHZZ + 2 * NZ + NS * NZ;
-        h->pd[ip]->erec0 = (int32_t)rec_slot.size();
-        int found[2] = {0, 0};
-        for (int edge = 0; edge < 2; ++edge) {
-          const int64_t node = edge ? P.N - 1 : 0;
-          for (int site = 0; site < NE; ++site) {
-            int64_t slot = -1;
-            if (site < NHZZ) {
-              slot = edge ? P.hslotN[site] : P.hslot0[site];
-            } else {
-              const int64_t base = P.hoff[NZ + (site - NHZZ)];   // t strips (j, z) then s strips (l, z)
-              if (base >= 0) slot = base + node;
-            }
-            auto it = slot >= 0 ? term_of_slot.find(slot) : term_of_slot.end();
-            if (it == term_of_slot.end()) continue;
-            rec_slot.push_back(slot);
-            rec_term.push_back(it->second);
-            term_of_slot.erase(it);
-            ++found[edge];
-          }
-        }
-        if (d->phases[ip].n_edge_rec[0] != found[0] || d->phases[ip].n_edge_rec[1] != found[1])
-          throw std::runtime_error("the phase descriptor's edge-record counts do not match the Hessian pattern "
-                                   "(codegen.edge_flags and pc_pattern.hpp disagree)");
-      }
-      if (!term_of_slot.empty())
-        throw std::runtime_error("internal error: an endpoint Hessian term lands on an edge-node entry no tile produces");
-      h->n_rec = (int32_t)rec_slot.size();
+    {   // the edge records (Shape::rec_slot): never an empty buffer
+      std::vector<int64_t> rec_slot(h->rec_slot);
+      std::vector<int32_t> rec_term(h->rec_term);
       if (rec_slot.empty()) { rec_slot.push_back(-1); rec_term.push_back(-1); }
       h->d_rec_slot.upload(rec_slot);
       h->d_rec_term.upload(rec_term);
@@ -1104,19 +741,6 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
     h->d_pt_hslot.upload(Q.pt_hslot);
     h->d_pt_hlocal.upload(Q.pt_hlocal);
     h->d_g_indptr.upload(Q.g_indptr);
-    const size_t nG = Q.g_row.size(), nH = Q.h_row.size();
-    {
-      // every part starts on a 256-byte boundary (what a separate allocation would give the kernels)
-      auto up = [](size_t v) { return (v + 31) & ~(size_t)31; };
-      h->o_lam = up(Q.num_x);
-      h->in_total = h->o_lam + up(Q.num_c);
-      h->o_f = 0;
-      h->o_gn = 1;
-      h->o_c = up(1 + Q.jgrad_col.size());
-      h->o_G = h->o_c + up(Q.num_c);
-      h->o_H = h->o_G + up(nG);
-      h->out_total = h->o_H + up(nH);
-    }
     h->d_in.alloc(h->in_total); h->d_out.alloc(h->out_total);
     h->h_in.alloc(h->in_total); h->h_out.alloc(h->out_total);
     h->d_norms.alloc(Q.num_c); h->h_norms.alloc(Q.num_c);
@@ -1127,7 +751,7 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
     HIP_OK(hipEventCreateWithFlags(&h->ev_small, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&h->ev_G, hipEventDisableTiming));
     if (const char* env = std::getenv("PYCOLLO_AMD_HOST_MODE")) h->host_mode = std::atoi(env) & 3;
-    if (h->resident && (Q.ph.size() > 1 ? h->bulk_all_res_fn != nullptr : h->pd[0]->fn_res != nullptr)) h->n_launches = 1;
+    if (has_resident_kernel(h.get())) h->n_launches = 1;
   });
   if (!ok) return 0;
   *out = h.release();

@@ -21,7 +21,8 @@ EXE = os.path.join(ROOT, "tests", "_build", "deriv_plan_sanitize")
 
 @pytest.fixture(scope="module")
 def harness():
-    deps = [SRC] + [os.path.join(ROOT, "pycollo_amd", "csrc", f) for f in ("pc_deriv.hpp", "pc_desc.hpp", "pc_pattern.hpp", "pc_args.h")]
+    deps = [SRC] + [os.path.join(ROOT, "pycollo_amd", "csrc", f) for f in ("pc_deriv.hpp", "pc_desc.hpp", "pc_eval_shape.hpp", "pc_pattern.hpp", "pc_args.h")]
+    deps.append(os.path.join(ROOT, "tests", "c", "desc_reader.hpp"))
     deps.append(os.path.join(ROOT, "include", "pycollo_amd.h"))
     if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
         os.makedirs(os.path.dirname(EXE), exist_ok=True)
@@ -58,7 +59,7 @@ def test_deriv_plan_under_asan_ubsan(harness, tmp_path, name, kw, refined):
     eng = NlpEngine(prob, device=None)
     desc = eng._make_desc(None, 0)
     fin, fout = str(tmp_path / "in.txt"), str(tmp_path / "out.txt")
-    _serialise(eng, desc, eng.info["threads_per_block"], fin)
+    _serialise(eng, desc, fin)
     res = subprocess.run([harness, fin, fout], capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-3000:]
     assert "ERROR: AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-3000:]

@@ -22,7 +22,8 @@ EXE = os.path.join(ROOT, "tests", "_build", "pattern_sanitize")
 
 @pytest.fixture(scope="module")
 def harness():
-    deps = [SRC] + [os.path.join(ROOT, "pycollo_amd", "csrc", f) for f in ("pc_desc.hpp", "pc_pattern.hpp", "pc_args.h")]
+    deps = [SRC] + [os.path.join(ROOT, "pycollo_amd", "csrc", f) for f in ("pc_desc.hpp", "pc_eval_shape.hpp", "pc_pattern.hpp", "pc_args.h")]
+    deps.append(os.path.join(ROOT, "tests", "c", "desc_reader.hpp"))
     deps.append(os.path.join(ROOT, "include", "pycollo_amd.h"))
     if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
         os.makedirs(os.path.dirname(EXE), exist_ok=True)
@@ -38,12 +39,19 @@ def _arr(ptr, n):
     return [] if not ptr or n <= 0 else [ptr[i] for i in range(n)]
 
 
-def _serialise(eng, desc, tile_nodes, path):
-    """The descriptor the library received, as the harness's text format."""
+# pc_eval_shape.hpp::Knobs as the last tokens of the text format (None: not set), with the library's defaults
+KNOBS = dict(tb=None, wpt=None, tile_nodes=None, two_wave=1, two_wave_max_tiles=1 << 30, two_wave_tiles=896,
+             two_wave_max_waves=2048, mix_min_run_rows=None, mix_cap_rows=32, resident=1, tail_blocks=0, merge=1,
+             lds_limit=64 * 1024)
+
+
+def _serialise(eng, desc, path, knobs=None, eval_ops=None, n_edge_rec=None):
+    """The descriptor the library received, as the harness's text format (tests/c/desc_reader.hpp).  ``knobs``: values
+    of KNOBS that differ from the defaults; ``eval_ops`` / ``n_edge_rec``: per phase, in place of the descriptor's."""
     tok = []
     qa_total = sum((n - 1) * n for n in _arr(desc.orders, desc.n_orders))
     qw_total = sum(_arr(desc.orders, desc.n_orders))
-    tok += [desc.n_phases, desc.n_s, desc.n_point, desc.n_b, desc.n_jgrad, desc.n_bjac, desc.n_pthess, tile_nodes, qa_total, qw_total]
+    tok += [desc.n_phases, desc.n_s, desc.n_point, desc.n_b, desc.n_jgrad, desc.n_bjac, desc.n_pthess, qa_total, qw_total]
     for ip in range(desc.n_phases):
         s = desc.phases[ip]
         tok += [s.n_y, s.n_u, s.n_q, s.n_p, s.t0_free, s.tF_free, s.K, s.n_jac, s.n_hess, s.n_w, s.compiled_order]
@@ -58,6 +66,17 @@ def _serialise(eng, desc, tile_nodes, path):
     tok += _arr(desc.point_phase, desc.n_point) + _arr(desc.point_kind, desc.n_point) + _arr(desc.point_idx, desc.n_point)
     tok += _arr(desc.jgrad_col, desc.n_jgrad) + _arr(desc.bjac_row, desc.n_bjac) + _arr(desc.bjac_col, desc.n_bjac)
     tok += _arr(desc.pthess_row, desc.n_pthess) + _arr(desc.pthess_col, desc.n_pthess)
+    # the launch shape's inputs
+    tok += [desc.two_wave_occupancy, desc.threads_per_block, desc.plan_only, desc.n_orders] + _arr(desc.orders, desc.n_orders)
+    tok += [repr(float(v)) for v in _arr(desc.quad_w, qw_total)]
+    for ip in range(desc.n_phases):
+        s = desc.phases[ip]
+        tok += [s.eval_ops if eval_ops is None else eval_ops[ip]]
+        tok += [s.n_edge_rec[0], s.n_edge_rec[1]] if n_edge_rec is None else list(n_edge_rec[ip])
+    kn = dict(KNOBS, **(knobs or {}))
+    assert set(kn) == set(KNOBS)
+    for key, v in kn.items():
+        tok += ([0, 0] if v is None else [1, v]) if KNOBS[key] is None else [v]
     with open(path, "w") as f:
         f.write(" ".join(str(t) for t in tok) + "\n")
 
@@ -113,7 +132,7 @@ def test_pattern_builder_under_asan_ubsan(built, harness, tmp_path, name, kw, ra
     desc = eng._make_desc(None, 0)
     tile_nodes = eng.info["threads_per_block"]
     fin, fout = str(tmp_path / "in.txt"), str(tmp_path / "out.txt")
-    _serialise(eng, desc, tile_nodes, fin)
+    _serialise(eng, desc, fin)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     res = subprocess.run([harness, fin, fout], capture_output=True, text=True, env=env, timeout=600)
     assert res.returncode == 0, res.stderr[-4000:]
@@ -141,11 +160,11 @@ def test_harness_reports_a_planted_overflow(harness, tmp_path):
     eng = NlpEngine(prob, device=None)
     desc = eng._make_desc(None, 0)
     fin, fout = str(tmp_path / "in.txt"), str(tmp_path / "out.txt")
-    _serialise(eng, desc, 64, fin)
+    _serialise(eng, desc, fin)
     toks = open(fin).read().split()
-    # header (10) + phase header (11 + 6) + K n_k + K h_k, then the first jac_row: make it a row far outside n_fn
+    # header (9) + phase header (11 + 6) + K n_k + K h_k, then the first jac_row: make it a row far outside n_fn
     K = desc.phases[0].K
-    toks[10 + 17 + 2 * K] = "1000"
+    toks[9 + 17 + 2 * K] = "1000"
     open(fin, "w").write(" ".join(toks) + "\n")
     res = subprocess.run([harness, fin, fout], capture_output=True, text=True, timeout=600)
     assert res.returncode != 0
@@ -173,7 +192,7 @@ def test_mixed_tile_cutter_under_asan_ubsan(built, harness, tmp_path, name, spec
     eng = NlpEngine(prob, device=None, mixed=tuple(spec for _ in prob.phases))
     desc = eng._make_desc(None, 0)
     fin, fout = str(tmp_path / "in.txt"), str(tmp_path / "out.txt")
-    _serialise(eng, desc, eng.info["threads_per_block"], fin)
+    _serialise(eng, desc, fin)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     res = subprocess.run([harness, fin, fout], capture_output=True, text=True, env=env, timeout=600)
     assert res.returncode == 0, res.stderr[-4000:]
@@ -197,7 +216,7 @@ def test_fixed_tile_table_under_asan_ubsan(built, harness, tmp_path):
     eng = ls.engine
     desc = eng._make_desc(None, eng.info["threads_per_block"])
     fin, fout = str(tmp_path / "in.txt"), str(tmp_path / "out.txt")
-    _serialise(eng, desc, eng.info["threads_per_block"], fin)
+    _serialise(eng, desc, fin)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     res = subprocess.run([harness, fin, fout], capture_output=True, text=True, env=env, timeout=600)
     assert res.returncode == 0, res.stderr[-4000:]
