@@ -128,8 +128,17 @@ typedef struct {
                                       (the tail inside the one launch); bit 1: pc_tail_big was the separate tail; bit 2:
                                       one launch covered every phase of a multi-phase problem; bits 4-6: workgroups of the
                                       resident tail (0 when the tail was a launch of its own or did not run); bits 8-11:
-                                      threads / 64 of the workgroup that ran the tail */
+                                      threads / 64 of the workgroup that ran the tail (PC_LAUNCH_* below) */
 } pc_info;
+
+/* the fields of pc_info.last_launch */
+#define PC_LAUNCH_RESIDENT 1            /* bit 0 */
+#define PC_LAUNCH_TAIL_BIG 2            /* bit 1 */
+#define PC_LAUNCH_MERGED 4              /* bit 2 */
+#define PC_LAUNCH_TAIL_BLOCKS_SHIFT 4   /* bits 4-6: (last_launch >> shift) & mask */
+#define PC_LAUNCH_TAIL_BLOCKS_MASK 7
+#define PC_LAUNCH_TAIL_WAVES_SHIFT 8    /* bits 8-11: threads / 64 */
+#define PC_LAUNCH_TAIL_WAVES_MASK 15
 
 const char* pc_last_error(void);
 

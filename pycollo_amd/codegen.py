@@ -425,8 +425,8 @@ def generate_source(model: Model, orders=None, heavy_cap: bool | None = None, mi
         hv = _heavy_attr(is_heavy(pm), heavy_cap)
         parts.append(f'#if PC_PART < 0 || PC_PART == {1}')
         parts.append(f'extern "C" __global__ void __launch_bounds__(256) {occ}{hv}pc_bulk_p{pm.index}_r({lead_sig}, PcPhaseArgs a, PcTailArgs t) {{')
-        parts.append('  const int ntb = (wa >> 28) & 7;   // leading workgroups that run the tail')
-        parts.append('  if ((int)blockIdx.x < ntb) { gen::Tail::run<true>(t, nullptr, (int)sizeof(PcBulkArgs), (int)blockIdx.x, ntb); return; }')
+        parts.append('  const int ntb = pc_wa_tail_blocks(wa);   // leading workgroups that run the tail')
+        parts.append('  if ((int)blockIdx.x < ntb) { gen::Tail::run<true>(t, nullptr, (int)offsetof(PcBulkTailArgs, t), (int)blockIdx.x, ntb); return; }')
         if mixed[pm.index]:
             parts.append('  const PcPhaseArgs& ka = pc::kernarg_phase_args();')
             parts.append('  const int blk = pc::xcd_major((int)blockIdx.x - ntb, n_blocks);')
@@ -444,13 +444,13 @@ def generate_source(model: Model, orders=None, heavy_cap: bool | None = None, mi
         for wn in static_ws:
             parts.append(f'#if PC_PART < 0 || PC_PART == {2 + static_ws.index(wn)}')
             parts.append(f'extern "C" __global__ void __launch_bounds__(256) {occ}{hv}pc_bulk_p{pm.index}_r_w{wn}({lead_sig}, PcPhaseArgs a, PcTailArgs t) {{')
-            parts.append('  const int ntb = (wa >> 28) & 7;')
-            parts.append('  if ((int)blockIdx.x < ntb) { gen::Tail::run<true>(t, nullptr, (int)sizeof(PcBulkArgs), (int)blockIdx.x, ntb); return; }')
+            parts.append('  const int ntb = pc_wa_tail_blocks(wa);')
+            parts.append('  if ((int)blockIdx.x < ntb) { gen::Tail::run<true>(t, nullptr, (int)offsetof(PcBulkTailArgs, t), (int)blockIdx.x, ntb); return; }')
             if mixed[pm.index]:
                 parts.append('  const PcPhaseArgs& ka = pc::kernarg_phase_args();')
             else:
                 parts.append('  const PcLead ld{xz, lamd, qa, sec_h, N, K, tile_begin, n_blocks, wa, wb};')
-            parts.append(f'  if (((wa >> 8) & 0xf) != {wn}) return;   // (built for exactly that many waves per tile; the host checks too)')
+            parts.append(f'  if (pc_wa_wpt(wa) != {wn}) return;   // (built for exactly that many waves per tile; the host checks too)')
             parts.append('  const int blk = pc::xcd_major((int)blockIdx.x - ntb, n_blocks);')
             parts.append('  switch (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6)) {')
             for wv in range(wn):
@@ -505,7 +505,7 @@ def generate_source(model: Model, orders=None, heavy_cap: bool | None = None, mi
         parts.append("// the same with the resident tail as block 0")
         parts.append(f'#if PC_PART < 0 || PC_PART == {2}')
         parts.append('extern "C" __global__ void __launch_bounds__(256) ' + occ + hva + 'pc_bulk_all_r(' + multi_sig + ', PcTailArgs t) {')
-        parts.append('  if ((int)blockIdx.x < tail_blocks) { gen::Tail::run<true>(t, nullptr, (int)((sizeof(PcMultiArgs) + 7) & ~7), (int)blockIdx.x, tail_blocks); return; }')
+        parts.append('  if ((int)blockIdx.x < tail_blocks) { gen::Tail::run<true>(t, nullptr, (int)offsetof(PcMultiTailArgs, t), (int)blockIdx.x, tail_blocks); return; }')
         parts += all_body(True)
         parts.append("}")
         parts.append('#endif')
@@ -515,7 +515,7 @@ def generate_source(model: Model, orders=None, heavy_cap: bool | None = None, mi
         for wn in multi_ws:
             parts.append(f'#if PC_PART < 0 || PC_PART == {3 + multi_ws.index(wn)}')
             parts.append(f'extern "C" __global__ void __launch_bounds__(256) {occ}{hva}pc_bulk_all_r_w{wn}(' + multi_sig + ', PcTailArgs t) {')
-            parts.append('  if ((int)blockIdx.x < tail_blocks) { gen::Tail::run<true>(t, nullptr, (int)((sizeof(PcMultiArgs) + 7) & ~7), (int)blockIdx.x, tail_blocks); return; }')
+            parts.append('  if ((int)blockIdx.x < tail_blocks) { gen::Tail::run<true>(t, nullptr, (int)offsetof(PcMultiTailArgs, t), (int)blockIdx.x, tail_blocks); return; }')
             parts += all_body(True, wn)
             parts.append("}")
             parts.append('#endif')

@@ -3,12 +3,23 @@
 #ifndef PC_ARGS_H
 #define PC_ARGS_H
 
+#include <stddef.h>
 #include <stdint.h>
+
+#ifdef __HIPCC__
+#define PC_HD __host__ __device__
+#else
+#define PC_HD
+#endif
 
 #define PC_MAX_ORDER 20
 #define PC_FLAG_C 1
 #define PC_FLAG_G 2
 #define PC_FLAG_H 4
+#define PC_MAX_BLOCK_THREADS 256   // largest workgroup of any launch: threads per block (64, 128 or 256) x waves per tile,
+                                   // and more than one wave shares a tile only at 64 threads per block
+#define PC_MAX_WPT 4               // waves per tile: 1, 2 or 4
+#define PC_MAX_TAIL_BLOCKS 4       // workgroups of the resident tail (pc_eval_shape.hpp::TAIL_PARTS)
 
 // One record per workgroup of a launch over a phase whose sections differ in order and whose code object carries
 // order-specialised tile bodies next to the any-order one ("mixed" build, codegen): which body runs the tile and where
@@ -96,10 +107,7 @@ struct PcPhaseArgs {
 struct LdsPlan {
   int qa, qw, off, tab, h, E, s, kr, cp, f, yu, fs, lam, red, out, total;
 };
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-inline LdsPlan lds_plan(int TB, int qa_total, int qw_total, int NY, int NFS, int NRED, int lds_out, int tab_doubles,
+PC_HD inline LdsPlan lds_plan(int TB, int qa_total, int qw_total, int NY, int NFS, int NRED, int lds_out, int tab_doubles,
                         bool mesh_tables, bool mixed = false) {
   LdsPlan p;
   int o = 0;
@@ -136,10 +144,7 @@ inline LdsPlan lds_plan(int TB, int qa_total, int qw_total, int NY, int NFS, int
 // else the fewest passes with which the full tile fits.  The kernels and the host's LDS sizing (pc_desc.hpp) both
 // call this.
 #define PC_STAGE_BUDGET 4480   // doubles: 2 regions x 17.5 KiB
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-constexpr int pc_row_passes(int n, int max_row_len) {
+PC_HD constexpr int pc_row_passes(int n, int max_row_len) {
   if (n < 3 || max_row_len <= 0) return 1;
   const int nq = 63 / (n - 1);   // sections of a full tile
   if (20 * (PC_STAGE_BUDGET / 2 / max_row_len) >= 17 * nq * (n - 1)) return 1;
@@ -148,10 +153,7 @@ constexpr int pc_row_passes(int n, int max_row_len) {
   return np;
 }
 // rows a pass holds
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-constexpr int pc_row_group(int n, int max_row_len) {
+PC_HD constexpr int pc_row_group(int n, int max_row_len) {
   const int np = pc_row_passes(n, max_row_len);
   return (n - 1 + np - 1) / np;
 }
@@ -165,9 +167,50 @@ struct PcLead {
   const double* qa;     // packed A tables, the packed weight tables right behind them (qw == qa + qa_total)
   const double* sec_h;  // section widths
   int32_t N, K, tile_begin, n_blocks;
-  int32_t wa;           // flags | wpt << 8 | (block_threads / 64) << 12 | spt << 16 | tail blocks (resident build) << 28
-  int32_t wb;           // uniform order n: qa_off[n] | (qa_total + qw_off[n]) << 16 (both relative to qa); else 0
+  int32_t wa;           // pc_lead_wa: flags, waves per tile, block threads / 64, sections per tile, tail blocks
+  int32_t wb;           // pc_lead_wb: uniform order n's A-table offset and absolute weight-table offset; else 0
 };
+static_assert(sizeof(PcLead) == 56, "PcLead is the 14 dwords the command processor preloads");
+
+// The two packed words of PcLead.  These functions are the only place their shifts and masks are written: the host packs
+// with them (pc_eval_launch.hpp), pc::bulk and the generated entry points unpack with them.
+//   wa  bits 0-7 flags (PC_FLAG_*) | 8-11 waves per tile | 12-15 block threads / 64 | 16-27 sections per tile of a
+//       uniform mesh | 28-30 leading workgroups that run the tail (resident build; bit 31 stays clear)
+//   wb  bits 0-15 qa_off[n] | 16-30 qa_total + qw_off[n], both in doubles from PcLead::qa (bit 31 stays clear:
+//       the unpacking shift is arithmetic)
+PC_HD constexpr int32_t pc_lead_wa(int flags, int wpt, int block_threads, int spt, int tail_blocks) {
+  return flags | (wpt << 8) | ((block_threads >> 6) << 12) | (spt << 16) | (tail_blocks << 28);
+}
+PC_HD constexpr int pc_wa_flags(int wa) { return wa & 0xff; }
+PC_HD constexpr int pc_wa_wpt(int wa) { return (wa >> 8) & 0xf; }
+PC_HD constexpr int pc_wa_block_threads(int wa) { return ((wa >> 12) & 0xf) << 6; }
+PC_HD constexpr int pc_wa_spt(int wa) { return (wa >> 16) & 0xfff; }
+PC_HD constexpr int pc_wa_tail_blocks(int wa) { return (wa >> 28) & 7; }
+PC_HD constexpr int32_t pc_lead_wb(int qa_off, int qw_abs) { return qa_off | (qw_abs << 16); }
+PC_HD constexpr int pc_wb_qa_off(int wb) { return wb & 0xffff; }
+PC_HD constexpr int pc_wb_qw_abs(int wb) { return wb >> 16; }
+// The largest value every field can take, from the constants that bound it, and that it fits its bits.  Sections per
+// tile: a tile holds at most as many nodes as its workgroup has threads and a section has at least one row.  Table
+// offsets: the A tables of every order 2 .. PC_MAX_ORDER are sum (n - 1) n doubles, the weight tables sum n.
+#define PC_LEAD_MAX_SPT (PC_MAX_BLOCK_THREADS - 1)
+#define PC_MAX_QA_TOTAL ((PC_MAX_ORDER - 1) * PC_MAX_ORDER * (PC_MAX_ORDER + 1) / 3)
+#define PC_MAX_QW_TOTAL (PC_MAX_ORDER * (PC_MAX_ORDER + 1) / 2 - 1)
+static_assert((PC_FLAG_C | PC_FLAG_G | PC_FLAG_H) <= 0xff, "PcLead::wa: flags have 8 bits");
+static_assert(PC_MAX_WPT <= 0xf, "PcLead::wa: waves per tile have 4 bits");
+static_assert(PC_MAX_BLOCK_THREADS / 64 <= 0xf, "PcLead::wa: block threads / 64 have 4 bits");
+static_assert(PC_LEAD_MAX_SPT <= 0xfff, "PcLead::wa: sections per tile have 12 bits");
+static_assert(PC_MAX_TAIL_BLOCKS <= 7, "PcLead::wa: tail blocks have 3 bits");
+static_assert(PC_MAX_QA_TOTAL == 2660 && PC_MAX_QA_TOTAL <= 0xffff, "PcLead::wb: the A-table offset has 16 bits");
+static_assert(PC_MAX_QA_TOTAL + PC_MAX_QW_TOTAL <= 0x7fff, "PcLead::wb: the weight-table offset has 15 bits and a sign");
+// what the host checks when it rebuilds the argument blocks (never per call: flags are the only per-call field)
+constexpr bool pc_lead_wa_fits(int wpt, int block_threads, int spt, int tail_blocks) {
+  return (wpt == 1 || wpt == 2 || wpt == 4) && block_threads >= 64 && block_threads <= PC_MAX_BLOCK_THREADS &&
+         block_threads % 64 == 0 && spt >= 0 && spt <= PC_LEAD_MAX_SPT && tail_blocks >= 0 && tail_blocks <= PC_MAX_TAIL_BLOCKS;
+}
+constexpr bool pc_lead_wb_fits(int qa_off, int qw_abs) {
+  return qa_off >= 0 && qa_off <= PC_MAX_QA_TOTAL && qw_abs >= 0 && qw_abs <= PC_MAX_QA_TOTAL + PC_MAX_QW_TOTAL;
+}
+
 // what the host hands to pc_bulk_p<i>: (lead scalars..., PcPhaseArgs a)
 struct PcBulkArgs {
   PcLead lead;
@@ -263,14 +306,28 @@ struct PcTailLead {
   int64_t x_off0;
   int32_t n_tiles0, N0, flags, block_threads;
 };
+static_assert(sizeof(PcTailLead) == 48, "PcTailLead is the 12 dwords the command processor preloads");
 struct PcTailLaunch {   // what the host hands to pc_tail: (lead scalars..., PcTailArgs a)
   PcTailLead lead;
   PcTailArgs t;
 };
+// What the host hands to the resident launches, whose leading workgroups run the tail: the bulk arguments with the tail's
+// behind them.  The tail finds its block by offsetof(..., t) (gen::Tail::run's arg_off).
+struct PcBulkTailArgs {    // pc_bulk_p<i>_r, pc_bulk_p<i>_r_w<W>: (lead scalars..., PcPhaseArgs a, PcTailArgs t)
+  PcBulkArgs b;
+  PcTailArgs t;
+};
+struct PcMultiTailArgs {   // pc_bulk_all_r, pc_bulk_all_r_w<W>: (PcMultiArgs member by member..., PcTailArgs t)
+  PcMultiArgs m;
+  PcTailArgs t;
+};
+static_assert(offsetof(PcBulkTailArgs, t) == sizeof(PcBulkArgs), "kernel argument layout: PcTailArgs right behind PcBulkArgs");
+static_assert(offsetof(PcMultiTailArgs, t) == ((sizeof(PcMultiArgs) + 7) & ~(size_t)7),
+              "kernel argument layout: PcTailArgs on the next 8-byte boundary behind PcMultiArgs");
 
 // What a kernel that reads a finished NLP point (pc_solution.hpp) must know about a phase to unscale it: the point, the
-// phase's place in it, its mesh and its variable scaling.  The host fills it from the handle (pc_engine.hip,
-// fill_phase_view); every argument block below embeds one.
+// phase's place in it, its mesh and its variable scaling.  The host fills it (pc_eval_launch.hpp,
+// phase_view); every argument block below embeds one.
 struct PcPhaseView {
   const double* x;          // [num_x] scaled NLP point
   const int32_t* sec_s;     // [K+1] first node of every section; sec_s[K] = N - 1

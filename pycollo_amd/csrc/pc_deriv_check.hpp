@@ -508,8 +508,8 @@ int pc_check_derivatives_device(pc_handle* h, const double* d_x, double obj_fact
     require_device(h);
     if (!d_x || !report) throw std::runtime_error("null x or report");
     for (size_t ip = 0; ip < h->pd.size(); ++ip) {
-      const auto& pd = *h->pd[ip];
-      if (pd.tile_begin != 0 || pd.tile_end != pd.n_tiles || pd.partials_ext)
+      const pcl::Range& rg = h->rg[ip];
+      if (rg.tile_begin != 0 || rg.tile_end != h->ph[ip].n_tiles || rg.partials_ext)
         throw std::runtime_error("derivative check: phase " + std::to_string(ip) +
                                  " is restricted to a tile range (or hands its partial sums to the caller); a check needs "
                                  "the whole NLP");
@@ -534,7 +534,11 @@ int pc_check_derivatives_device(pc_handle* h, const double* d_x, double obj_fact
     }
     deriv_handover(h, D, 0, st);
     // analytic values at x~
-    launch_all(h, d_x, lam, D.c0.p, D.G0.p, D.H0.p, D.f3.p + 2, D.gn0.p, PC_FLAG_C | PC_FLAG_G | PC_FLAG_H, st, sigma);
+    pcl::Call call = device_call(h, d_x, lam, D.c0.p, D.G0.p, D.H0.p);
+    call.fobj = D.f3.p + 2;
+    call.grad_nz = D.gn0.p;
+    call.sigma = sigma;
+    launch_all(h, call, st);
     const double* Gan = d_jac_override ? d_jac_override : D.G0.p;
     const double* Han = d_hess_override ? d_hess_override : D.H0.p;
     const double* Jan = o.d_jgrad_override ? o.d_jgrad_override : D.gn0.p;
@@ -552,8 +556,15 @@ int pc_check_derivatives_device(pc_handle* h, const double* d_x, double obj_fact
                          D.step2.p, D.cols.p + prev0, n_prev, D.cols.p + c0, nc, delta);
       prev0 = c0;
       n_prev = nc;
-      launch_all(h, D.xp.p, nullptr, D.cP.p, D.GP.p, nullptr, D.f3.p, D.gnP.p, PC_FLAG_C | PC_FLAG_G, st, sigma);
-      launch_all(h, D.xm.p, nullptr, D.cM.p, D.GM.p, nullptr, D.f3.p + 1, D.gnM.p, PC_FLAG_C | PC_FLAG_G, st, sigma);
+      pcl::Call plus = device_call(h, D.xp.p, nullptr, D.cP.p, D.GP.p, nullptr), minus = device_call(h, D.xm.p, nullptr, D.cM.p, D.GM.p, nullptr);
+      plus.fobj = D.f3.p;
+      plus.grad_nz = D.gnP.p;
+      minus.fobj = D.f3.p + 1;
+      minus.grad_nz = D.gnM.p;
+      plus.flags = minus.flags = PC_FLAG_C | PC_FLAG_G;
+      plus.sigma = minus.sigma = sigma;
+      launch_all(h, plus, st);
+      launch_all(h, minus, st);
       const int64_t nch = D.ch_ptr[k + 1] - D.ch_ptr[k], nmr = D.mr_ptr[k + 1] - D.mr_ptr[k];
       if (nch > 0)
         hipLaunchKernelGGL(deriv_lagrangian_grad, dim3(deriv_grid(64 * nch)), dim3(DERIV_THREADS), 0, st,

@@ -18,6 +18,7 @@
 #include "pc_pattern.hpp"
 #include "pc_desc.hpp"
 #include "pc_eval_shape.hpp"
+#include "pc_eval_launch.hpp"
 #include "pc_deriv.hpp"
 #include "pc_solution_plan.hpp"
 
@@ -30,18 +31,14 @@ thread_local std::string g_err;
 
 void set_err(const std::string& s) { g_err = s; }
 
-// a phase's share of the launch shape (pc_eval_shape.hpp) and what the device holds for it
-struct PhaseDev : pce::PhaseShape {
+// what the device holds for a phase
+struct PhaseDev {
   DevBuf<int32_t> tile_k0, tile_n0, sec_s;
   DevBuf<double> sec_h, scal, partials, tab;
   DevBuf<int64_t> sec_E, hslot0, hslotN, hsum_slot;
   DevBuf<int32_t> hsum_local;
   DevBuf<unsigned long long> gran;   // resident tail: the per-tile partial sums as granules, [n_tiles][nred][2]
-  hipFunction_t fn = nullptr;
-  hipFunction_t fn_res = nullptr;    // single-phase problems: bulk kernel with the resident tail as block 0
-  int tile_begin = 0, tile_end = 0;  // launched tile range (whole phase unless sharded)
-  double* partials_ext = nullptr;    // caller-owned partial-sum buffer (sharded exchange), else `partials`
-  std::vector<double> scal_host;
+  hipFunction_t fn = nullptr;        // the phase's bulk kernel (pcl::BULK)
 };
 
 // generic kernel: 2-norm of every CSR row (scaling.py:392-395 without densifying)
@@ -97,24 +94,20 @@ struct pc_handle : pce::Shape {   // the launch shape pc_create decided (pc_eval
   pcp::Problem Q;
   int device = -1;
   bool scaling_set = false;
-  double w_J = 1.0;
   std::vector<double> qa, qw;   // quadrature tables
   // device
   hipStream_t stream = nullptr;
   hipModule_t module = nullptr;
   std::vector<hipModule_t> more_modules;   // a heavy model's code object comes in parts (<base>.p<k>.hsaco, codegen.n_parts)
-  hipFunction_t tail_fn = nullptr;
-  hipFunction_t tail_big_fn = nullptr;   // same kernel with the partial-sum loads of several strides in flight
-  hipFunction_t bulk_all_fn = nullptr;   // multi-phase problems: every phase's bulk kernel in one launch
-  DevBuf<char> d_phase_args;             // [n_phases] PcPhaseArgs read by pc_bulk_all
-  DevBuf<PcTileRec> d_trec;              // records of the launched tile ranges, in launch order
-  std::vector<int> trec_first;           // [n_phases] first record of each phase in d_trec
-  bool args_dirty = true;                // scaling / tile range / partials buffer changed since the last upload
-  // host-side argument blocks, filled once per change of scaling / tile range / partials buffer; a call only
-  // patches the caller's pointers, the flags and sigma into them
-  std::vector<PcBulkArgs> host_bulk_args;   // per phase: lead scalars + argument block, kept filled between calls
-  PcTailLaunch host_tail_launch;   // lead scalars + argument block of pc_tail, kept filled between calls
-  bool host_args_dirty = true;
+  // what the kernels are handed and how they are launched (pc_eval_launch.hpp)
+  hipFunction_t fn[pcl::N_KERNELS] = {};   // the kernels of the code object but the phases' own (PhaseDev::fn); null: absent
+  pcl::Have have;                          // ... which of them a plan may name
+  pcl::Range rg[PC_MAX_PHASES];            // launched tile range and caller-owned partial-sum buffer of every phase
+  pcl::Scaling scal;                       // host copies of the scaling: it travels by value in the argument blocks
+  pcl::Blocks blocks;                      // the argument blocks, kept filled between calls
+  bool blocks_dirty = true;                // scaling / tile range / partials buffer changed since they were built
+  DevBuf<char> d_phase_args;               // [n_phases] PcPhaseArgs read by pc_bulk_all: copy of blocks.merged
+  DevBuf<PcTileRec> d_trec;                // records of the launched tile ranges, in launch order
   std::vector<std::unique_ptr<PhaseDev>> pd;
   DevBuf<double> d_qa, d_pointV, d_pointr, d_Wend, d_norms;
   // the packed input and output blocks (Shape::o_lam ...), pinned on the host and mirrored on the device: one copy
@@ -132,14 +125,11 @@ struct pc_handle : pce::Shape {   // the launch shape pc_create decided (pc_eval
   bool G_copied = false;
   DevBuf<int64_t> d_point_x, d_tail_owned, d_pt_hslot, d_g_indptr;
   DevBuf<int32_t> d_pt_hlocal;
-  std::vector<double> h_pointV, h_pointr, h_Wend;   // host copies: travel by value in PcTailArgs
   // resident tail (pc_kernels.hpp, RES): one launch per evaluation, the tail runs as block 0 beside the tiles
-  hipFunction_t bulk_all_res_fn = nullptr;   // multi-phase problems: pc_bulk_all with the resident tail
   DevBuf<unsigned long long> d_erec;         // granules of the edge-node Hessian entries endpoint terms are added to
   DevBuf<int64_t> d_rec_slot;                // [n_rec] H slot of every record (-1: site absent)
   DevBuf<int32_t> d_rec_term;                // [n_rec] endpoint Hessian entry added to the record, or -1
   PinBuf<unsigned> h_timeout;                // host-visible: set by a tail whose granules never arrived
-  uint32_t epoch = 0;                        // tag of the last resident launch's granules (never 0)
   int spin_us = 500;                         // host-pointer calls poll the stream this long before blocking (PYCOLLO_AMD_SPIN_US)
   DevBuf<unsigned long long> d_hb_gran;      // endpoint Hessian terms handed between the tail's workgroups
   PinBuf<double> h_norms;
@@ -153,302 +143,77 @@ struct pc_handle : pce::Shape {   // the launch shape pc_create decided (pc_eval
 
 namespace {
 
-void fill_point_tables(pc_handle* h, PcTailArgs& t) {
-  auto& Q = h->Q;
-  for (size_t i = 0; i < Q.point_x.size(); ++i) {
-    t.pt_x[i] = Q.point_x[i];
-    t.pt_V[i] = h->h_pointV[i];
-    t.pt_r[i] = h->h_pointr[i];
-  }
-  for (size_t r = 0; r < h->h_Wend.size(); ++r) t.pt_W[r] = h->h_Wend[r];
-}
-
-void fill_tail_args(pc_handle* h, PcTailArgs& t, const double* d_x, const double* d_lam, double* d_c, double* d_G,
-                    double* d_H, double* d_fobj, double* d_gradnz, int flags, double sigma) {
-  auto& Q = h->Q;
-  std::memset(&t, 0, sizeof(t));
-  t.x = d_x;
-  t.lam = d_lam;
-  t.c = d_c;
-  t.G = d_G;
-  t.H = d_H;
-  t.fobj = d_fobj;
-  t.grad_nz = d_gradnz;
-  t.sigma = sigma;
-  t.wJ = h->w_J;
-  t.point_x = h->d_point_x.p;
-  t.point_V = h->d_pointV.p;
-  t.point_r = h->d_pointr.p;
-  t.W_end = h->d_Wend.p;
-  fill_point_tables(h, t);
-  t.tail_owned = h->d_tail_owned.p;
-  t.pt_hslot = h->d_pt_hslot.p;
-  t.pt_hlocal = h->d_pt_hlocal.p;
-  t.c_end_off = Q.c_end_off;
-  t.g_end_base = Q.g_end_base;
-  t.n_tail_owned = (int32_t)Q.tail_owned.size();
-  t.flags = flags;
-  t.block_threads = PC_TAIL_THREADS;
-  t.lds_nred = h->lds_nred;
-  t.erec = h->d_erec.p;
-  t.rec_slot = h->d_rec_slot.p;
-  t.rec_term = h->d_rec_term.p;
-  t.n_rec = h->n_rec;
-  t.n_tail_blocks = 1;
-  t.hb_gran = h->d_hb_gran.p;
-  t.timeout = h->h_timeout.p;
-  for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
-    auto& P = Q.ph[ip];
-    auto& D = *h->pd[ip];
-    PcTailPhase& tp = t.ph[ip];
-    tp.partials = D.partials_ext ? D.partials_ext : D.partials.p;
-    tp.gran = D.gran.p;
-    tp.scal = D.scal.p;
-    tp.x_off = P.x_off;
-    tp.s_off = Q.s_off;
-    tp.c_int_off = P.c_int_off;
-    for (int m = 0; m < 8; ++m) tp.gq_base[m] = P.gq_base[m];
-    tp.hsum_slot = D.hsum_slot.p;
-    tp.hsum_local = D.hsum_local.p;
-    tp.t_fixed[0] = P.t_fixed[0];
-    tp.t_fixed[1] = P.t_fixed[1];
-    tp.n_tiles = D.n_tiles;
-    tp.N = P.N;
-  }
-}
-
-// The argument block of one phase's bulk kernel (everything but the per-call pointers and flags when `d_x` is null).
-void fill_phase_args(pc_handle* h, size_t ip, PcPhaseArgs& a, const double* d_x, const double* d_lam, double* d_c,
-                     double* d_G, double* d_H, int flags, int wpt) {
-  auto& Q = h->Q;
-  auto& P = Q.ph[ip];
-  auto& D = *h->pd[ip];
-  std::memset(&a, 0, sizeof(a));
-  a.x = d_x;
-  a.lam = d_lam;
-  a.c = d_c;
-  a.G = d_G;
-  a.H = d_H;
-  a.tile_k0 = D.tile_k0.p;
-  a.tile_n0 = D.tile_n0.p;
-  a.sec_s = D.sec_s.p;
-  a.sec_h = D.sec_h.p;
-  a.sec_E = D.sec_E.p;
-  a.qa = h->d_qa.p;
-  a.qw = h->d_qa.p + h->qa.size();
-  if (D.scal_host.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
-  for (size_t i = 0; i < D.scal_host.size(); ++i) a.scal[i] = D.scal_host[i];
-  for (size_t i = 0; i < P.goff.size(); ++i) a.goff[i] = P.goff[i];
-  for (size_t i = 0; i < P.hoff.size(); ++i) a.hoff[i] = P.hoff[i];
-  a.uni_n = D.uni_n;
-  a.spt = D.spt;
-  a.lds_out = wpt == 4 ? D.lds_out4 : D.lds_out;
-  a.wpt = wpt;
-  a.hslot0 = D.hslot0.p;
-  a.hslotN = D.hslotN.p;
-  a.partials = D.partials_ext ? D.partials_ext : D.partials.p;
-  a.gran = D.gran.p;
-  a.erec = h->d_erec.p;
-  a.erec0 = D.erec0;
-  a.tab = D.tab.p;
-  a.tile_rec = (h->mixed && h->d_trec.p) ? h->d_trec.p + h->trec_first[ip] : nullptr;
-  a.x_off = P.x_off;
-  a.s_off = Q.s_off;
-  a.c_off = P.c_off;
-  a.c_path_off = P.c_path_off;
-  a.c_int_off = P.c_int_off;
-  a.t_fixed[0] = P.t_fixed[0];
-  a.t_fixed[1] = P.t_fixed[1];
-  a.N = P.N;
-  a.K = P.K;
-  a.n_tiles = D.n_tiles;
-  a.flags = flags;
-  a.tile_begin = D.tile_begin;
-  a.n_blocks = std::max(0, D.tile_end - D.tile_begin);
-  a.block_threads = h->TB * wpt;
-  a.qa_total = (int32_t)h->qa.size();
-  a.qw_total = (int32_t)h->qw.size();
-  std::memcpy(a.qa_off, h->qa_off, sizeof(a.qa_off));
-  std::memcpy(a.qw_off, h->qw_off, sizeof(a.qw_off));
-}
-
-// What the kernels that read a finished NLP point (pc_solution.hpp) know about a phase: the point d_x, the phase's place
-// in it, its mesh and the variable scaling the handle holds now.
-PcPhaseView fill_phase_view(pc_handle* h, int phase, const double* d_x) {
-  auto& P = h->Q.ph[phase];
-  auto& D = *h->pd[phase];
-  if (D.scal_host.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
-  PcPhaseView v;
-  std::memset(&v, 0, sizeof(v));
-  v.x = d_x;
-  v.sec_s = D.sec_s.p;
-  v.x_off = P.x_off;
-  v.s_off = h->Q.s_off;
-  v.t_fixed[0] = P.t_fixed[0];
-  v.t_fixed[1] = P.t_fixed[1];
-  v.N = P.N;
-  v.K = P.K;
-  for (size_t i = 0; i < D.scal_host.size(); ++i) v.scal[i] = D.scal_host[i];
-  return v;
-}
-
-// one kernel whose parameter is the argument block `args`, passed by value
-template <class Args>
-void launch_block(hipFunction_t fn, unsigned grid, unsigned block, size_t lds, hipStream_t stream, Args& args) {
-  size_t sz = sizeof(args);
-  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+// one kernel whose parameters are the argument block `args` of `bytes` bytes, passed by value
+void launch_block(hipFunction_t fn, unsigned grid, unsigned block, size_t lds, hipStream_t stream, void* args, size_t bytes) {
+  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
   HIP_OK(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, (unsigned)lds, stream, nullptr, cfg));
 }
-
-// the code object has the kernel that runs the tail beside the tiles, and the handle may use it
-bool has_resident_kernel(const pc_handle* h) {
-  return h->resident && (h->Q.ph.size() > 1 ? h->bulk_all_res_fn != nullptr : h->pd[0]->fn_res != nullptr);
+template <class Args>
+void launch_block(hipFunction_t fn, unsigned grid, unsigned block, size_t lds, hipStream_t stream, Args& args) {
+  launch_block(fn, grid, block, lds, stream, &args, sizeof(args));
 }
 
-void launch_all(pc_handle* h, const double* d_x, const double* d_lam, double* d_c, double* d_G, double* d_H,
-                double* d_fobj, double* d_gradnz, int flags, hipStream_t st, double sigma, bool bulk = true,
-                bool tail = true) {
-  auto& Q = h->Q;
-  // One launch per evaluation when every phase runs whole on this device: the tail is block 0 of the bulk launch and
-  // receives the tiles' partial sums as granules (pc_kernels.hpp, RES).  A rank of the section-sharded evaluation,
-  // whose sums travel through the all-gather first, and the bulk-only / tail-only calls take two launches.
-  bool res = bulk && tail && has_resident_kernel(h);
-  for (size_t ip = 0; res && ip < Q.ph.size(); ++ip) {
-    auto& D = *h->pd[ip];
-    res = D.tile_begin == 0 && D.tile_end == D.n_tiles && !D.partials_ext;
+// the device addresses the argument blocks hold (pc_eval_launch.hpp::Addr)
+pcl::Addr device_addresses(const pc_handle* h) {
+  pcl::Addr A;
+  A.qa = h->d_qa.p;
+  A.point_x = h->d_point_x.p;
+  A.point_V = h->d_pointV.p;
+  A.point_r = h->d_pointr.p;
+  A.W_end = h->d_Wend.p;
+  A.tail_owned = h->d_tail_owned.p;
+  A.pt_hslot = h->d_pt_hslot.p;
+  A.pt_hlocal = h->d_pt_hlocal.p;
+  A.erec = h->d_erec.p;
+  A.hb_gran = h->d_hb_gran.p;
+  A.rec_slot = h->d_rec_slot.p;
+  A.rec_term = h->d_rec_term.p;
+  A.timeout = h->h_timeout.p;
+  A.phase_args = reinterpret_cast<const PcPhaseArgs*>(h->d_phase_args.p);
+  A.trec = h->d_trec.p;
+  for (size_t ip = 0; ip < h->pd.size(); ++ip) {
+    const PhaseDev& D = *h->pd[ip];
+    A.ph[ip] = pcl::PhaseAddr{D.tile_k0.p, D.tile_n0.p, D.sec_s.p, D.sec_h.p, D.sec_E.p, D.hslot0.p, D.hslotN.p, D.hsum_slot.p,
+                              D.hsum_local.p, D.scal.p, D.tab.p, D.partials.p, D.gran.p};
   }
-  if (h->host_args_dirty) {
-    if (h->mixed) {   // the records of the launched tile ranges, in launch order (pc_args.h::PcTileRec)
-      std::vector<PcTileRec> recs;
-      h->trec_first.assign(Q.ph.size(), 0);
-      for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
-        auto& D = *h->pd[ip];
-        h->trec_first[ip] = (int)recs.size();
-        for (int t = D.tile_begin; t < D.tile_end; ++t) recs.push_back(h->trec_all[h->trec_base[ip] + t]);
-      }
-      if (recs.empty()) recs.push_back(PcTileRec{});
-      HIP_OK(hipDeviceSynchronize());   // no launch in flight may still read the old records
-      h->d_trec.upload(recs);
-    }
-    h->host_bulk_args.resize(Q.ph.size());
-    for (size_t ip = 0; ip < Q.ph.size(); ++ip)
-      fill_phase_args(h, ip, h->host_bulk_args[ip].a, nullptr, nullptr, nullptr, nullptr, nullptr, 0, h->pd[ip]->wpt);
-    fill_tail_args(h, h->host_tail_launch.t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1.0);
-    h->host_args_dirty = false;
+  return A;
+}
+
+PcPhaseView fill_phase_view(pc_handle* h, int phase, const double* d_x) {
+  return pcl::phase_view(h->Q, h->scal, device_addresses(h), phase, d_x);
+}
+
+// The scaling, a tile range or a partials buffer changed: the argument blocks, the device copy of the merged launch's
+// phase blocks and the uploaded tile records are rebuilt by the next launch.  The caller has synchronised the device.
+void invalidate_blocks(pc_handle* h) { h->blocks_dirty = true; }
+
+void refresh_blocks(pc_handle* h) {
+  const size_t n = h->Q.ph.size();
+  pcl::Records rec;
+  if (h->mixed) {
+    rec = pcl::launched_records(*h, h->rg, n);
+    HIP_OK(hipDeviceSynchronize());   // no launch in flight may still read the old records
+    h->d_trec.upload(rec.recs);
   }
-  auto patch_tail = [&](PcTailArgs& t, int block_threads) {
-    t.x = d_x; t.lam = d_lam; t.c = d_c; t.G = d_G; t.H = d_H;
-    t.fobj = d_fobj; t.grad_nz = d_gradnz; t.flags = flags; t.sigma = sigma;
-    t.block_threads = block_threads;
-    t.epoch = h->epoch;
-  };
-  if (res && ++h->epoch == 0) h->epoch = 1;   // (zero is the tag of never-written granules)
-  int last = 0;   // -> h->last_launch
-  struct MultiRes {
-    PcMultiArgs m;
-    PcTailArgs t;
-  };
-  if (bulk && (res ? h->bulk_all_res_fn : h->bulk_all_fn) && Q.ph.size() > 1) {
-    // several phases, one launch: the phases' workgroups run side by side instead of one kernel after another
-    if (h->args_dirty) {
-      std::vector<PcPhaseArgs> blocks(Q.ph.size());
-      for (size_t ip = 0; ip < Q.ph.size(); ++ip)
-        fill_phase_args(h, ip, blocks[ip], nullptr, nullptr, nullptr, nullptr, nullptr, 0, h->wpt_all);
-      HIP_OK(hipDeviceSynchronize());   // no launch in flight may still read the old blocks
-      HIP_OK(hipMemcpy(h->d_phase_args.p, blocks.data(), blocks.size() * sizeof(PcPhaseArgs), hipMemcpyHostToDevice));
-      h->args_dirty = false;
-    }
-    MultiRes mr;
-    PcMultiArgs& m = mr.m;
-    std::memset(&m, 0, sizeof(m));
-    m.x = d_x;
-    m.lam = d_lam;
-    m.c = d_c;
-    m.G = d_G;
-    m.H = d_H;
-    m.ph = reinterpret_cast<const PcPhaseArgs*>(h->d_phase_args.p);
-    m.flags = flags;
-    m.n_phases = (int32_t)Q.ph.size();
-    m.epoch = h->epoch;
-    m.trec = h->mixed ? h->d_trec.p : nullptr;
-    int nb = 0;
-    for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
-      m.first_block[ip] = nb;
-      nb += std::max(0, h->pd[ip]->tile_end - h->pd[ip]->tile_begin);
-    }
-    for (size_t ip = Q.ph.size(); ip <= PC_MAX_PHASES; ++ip) m.first_block[ip] = nb;
-    if (res) {
-      const int bt = h->TB * h->wpt_all;
-      const int ntb = h->tail_blocks_all;
-      m.tail_blocks = ntb;
-      mr.t = h->host_tail_launch.t;
-      patch_tail(mr.t, bt);
-      mr.t.n_tail_blocks = ntb;
-      size_t sz = sizeof(mr);
-      void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &mr, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-      HIP_OK(hipModuleLaunchKernel(h->bulk_all_res_fn, nb + ntb, 1, 1, bt, 1, 1,
-                                   std::max(h->lds_all, h->tail_lds_bytes), st, nullptr, cfg));
-      h->last_launch = 1 | 4 | (ntb << 4) | ((bt / 64) << 8);
-      return;
-    }
-    if (nb > 0) {
-      size_t sz = sizeof(m);
-      void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &m, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-      HIP_OK(hipModuleLaunchKernel(h->bulk_all_fn, nb, 1, 1, h->TB * h->wpt_all, 1, 1, h->lds_all, st, nullptr, cfg));
-    }
-    last |= 4;
-    bulk = false;
+  pcl::build_blocks(h->blocks, h->Q, *h, h->scal, h->rg, device_addresses(h), rec);
+  if (h->have.k[pcl::BULK_ALL]) {
+    HIP_OK(hipDeviceSynchronize());   // no launch in flight may still read the old blocks
+    HIP_OK(hipMemcpy(h->d_phase_args.p, h->blocks.merged.data(), n * sizeof(PcPhaseArgs), hipMemcpyHostToDevice));
   }
-  struct BulkRes {   // what the host hands to pc_bulk_p<i>_r: (lead scalars..., PcPhaseArgs a, PcTailArgs t)
-    PcBulkArgs ba;
-    PcTailArgs t;
-  };
-  for (size_t ip = 0; bulk && ip < Q.ph.size(); ++ip) {
-    auto& D = *h->pd[ip];
-    if (D.tile_end <= D.tile_begin) continue;
-    PcPhaseArgs& a = h->host_bulk_args[ip].a;
-    a.x = d_x; a.lam = d_lam; a.c = d_c; a.G = d_G; a.H = d_H;
-    a.flags = flags;
-    a.wpt = D.wpt;
-    a.block_threads = h->TB * D.wpt;
-    a.epoch = h->epoch;
-    // (lead scalars..., PcPhaseArgs): the lead is what the command processor preloads into SGPRs (pc_args.h)
-    PcBulkArgs& ba = h->host_bulk_args[ip];
-    const int un = a.uni_n > 0 ? a.uni_n : 0;
-    ba.lead = PcLead{a.x + a.x_off, a.lam ? a.lam + a.c_off : nullptr, a.qa, a.sec_h, a.N, a.K, a.tile_begin, a.n_blocks,
-                     a.flags | (a.wpt << 8) | ((a.block_threads >> 6) << 12) | (a.spt << 16),
-                     un ? (a.qa_off[un] | ((a.qa_total + a.qw_off[un]) << 16)) : 0};
-    if (res) {   // single phase (several phases were launched above)
-      static_assert(offsetof(BulkRes, t) == sizeof(PcBulkArgs), "kernel argument layout");
-      BulkRes br;
-      br.ba = ba;
-      br.t = h->host_tail_launch.t;
-      const int ntb = h->tail_blocks;
-      br.ba.lead.wa |= ntb << 28;
-      patch_tail(br.t, a.block_threads);
-      br.t.n_tail_blocks = ntb;
-      size_t sz = sizeof(br);
-      void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &br, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-      HIP_OK(hipModuleLaunchKernel(D.fn_res, D.n_tiles + ntb, 1, 1, a.block_threads, 1, 1,
-                                   std::max(D.lds_bytes, h->tail_lds_bytes), st, nullptr, cfg));
-      h->last_launch = 1 | (ntb << 4) | ((a.block_threads / 64) << 8);
-      return;
-    }
-    size_t sz = sizeof(ba);
-    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ba, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-    HIP_OK(hipModuleLaunchKernel(D.fn, D.tile_end - D.tile_begin, 1, 1, h->TB * D.wpt, 1, 1, D.lds_bytes, st, nullptr, cfg));
-  }
-  h->last_launch = last;
-  if (!tail) return;
-  PcTailLaunch& tl = h->host_tail_launch;
-  PcTailArgs& t = tl.t;
-  patch_tail(t, PC_TAIL_THREADS);
-  tl.lead = PcTailLead{t.x, t.ph[0].partials, t.ph[0].scal, t.ph[0].x_off, t.ph[0].n_tiles, t.ph[0].N, t.flags, t.block_threads};
-  size_t sz = sizeof(tl);
-  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &tl, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  hipFunction_t fn = (h->tail_big_fn && h->tail_big) ? h->tail_big_fn : h->tail_fn;
-  HIP_OK(hipModuleLaunchKernel(fn, 1, 1, 1, PC_TAIL_THREADS, 1, 1, h->tail_lds_bytes, st, nullptr, cfg));
-  h->last_launch = last | (fn == h->tail_big_fn ? 2 : 0) | ((PC_TAIL_THREADS / 64) << 8);
+  h->blocks_dirty = false;
+}
+
+hipFunction_t kernel_of(const pc_handle* h, const pcl::Launch& l) {
+  return l.kernel == pcl::BULK ? h->pd[l.phase]->fn : h->fn[l.kernel];
+}
+
+// One evaluation, or its tiles' or its tail's part: refresh what a change invalidated, plan the call, launch.
+void launch_all(pc_handle* h, const pcl::Call& call, hipStream_t st) {
+  if (h->blocks_dirty) refresh_blocks(h);
+  const pcl::Plan p = pcl::plan(h->blocks, *h, h->have, call);
+  for (int i = 0; i < p.n; ++i)
+    launch_block(kernel_of(h, p.l[i]), p.l[i].grid, p.l[i].block, p.l[i].lds, st, p.l[i].args, p.l[i].arg_bytes);
+  h->last_launch = p.last_launch;
 }
 
 void upload_scaling(pc_handle* h) {
@@ -471,7 +236,7 @@ void upload_scaling(pc_handle* h) {
     for (int l = 0; l < NS; ++l) s[o++] = h->r_ocp[P.wocp(l, Q.ocp_s_off)];
     const double* W = h->W_ocp.data() + P.ocp_c_off;
     for (int a = 0; a < NY + NP + NQ; ++a) s[o++] = W[a];
-    D.scal_host = s;
+    h->scal.phase[ip] = s;
     if (h->device >= 0) {
       if (D.scal.n != s.size()) D.scal.alloc(s.size());
       HIP_OK(hipMemcpy(D.scal.p, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -501,9 +266,9 @@ void upload_scaling(pc_handle* h) {
     h->d_pointV.upload(pv);
     h->d_pointr.upload(pr);
     h->d_Wend.upload(we);
-    h->h_pointV = pv;
-    h->h_pointr = pr;
-    h->h_Wend = we;
+    h->scal.pointV = pv;
+    h->scal.pointr = pr;
+    h->scal.Wend = we;
   }
   h->x_valid = h->fc_valid = false;
 }
@@ -547,6 +312,27 @@ void wait_stream(pc_handle* h) {
 const double* kx(pc_handle* h) { return (h->host_mode & 1) ? h->h_in.p : h->d_in.p; }
 const double* klam(pc_handle* h) { return kx(h) + h->o_lam; }
 double* kout(pc_handle* h, size_t off) { return ((h->host_mode & 2) ? h->h_out.p : h->d_out.p) + off; }
+// a device-pointer call: the caller's vectors, J into the handle's own output block; every flag unless the caller says
+pcl::Call device_call(pc_handle* h, const double* d_x, const double* d_lambda, double* d_g, double* d_jac, double* d_hess) {
+  pcl::Call call;
+  call.x = d_x; call.lam = d_lambda; call.c = d_g; call.G = d_jac; call.H = d_hess;
+  call.fobj = h->d_out.p + h->o_f;
+  call.flags = PC_FLAG_C | PC_FLAG_G | PC_FLAG_H;
+  return call;
+}
+// a host-pointer call that computes `flags`: the staged x~ (and lambda with PC_FLAG_H) in, the packed output block out
+pcl::Call host_call(pc_handle* h, int flags) {
+  pcl::Call call;
+  call.x = kx(h);
+  call.lam = (flags & PC_FLAG_H) ? klam(h) : nullptr;
+  call.c = (flags & PC_FLAG_C) ? kout(h, h->o_c) : nullptr;
+  call.G = (flags & PC_FLAG_G) ? kout(h, h->o_G) : nullptr;
+  call.H = (flags & PC_FLAG_H) ? kout(h, h->o_H) : nullptr;
+  call.fobj = kout(h, h->o_f);
+  call.grad_nz = kout(h, h->o_gn);
+  call.flags = flags;
+  return call;
+}
 
 // x~ of a callback: staged (and copied up) only when the caller says the point is new
 void stage_x(pc_handle* h, const double* x, int new_x) {
@@ -634,12 +420,11 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
     const pce::Knobs kn = read_knobs(d->device);
     static_cast<pce::Shape&>(*h) = pce::build_shape(*d, Q, kn);   // pc_eval_shape.hpp: plain C++, tested on the CPU
     h->pd.resize(Q.ph.size());
+    h->scal.phase.resize(Q.ph.size());
     for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
       h->pd[ip].reset(new PhaseDev());
-      static_cast<pce::PhaseShape&>(*h->pd[ip]) = h->ph[ip];
-      h->pd[ip]->tile_end = h->ph[ip].n_tiles;
+      h->rg[ip].tile_end = h->ph[ip].n_tiles;
     }
-    h->ph = {};   // (the phases' shapes live in pd from here on, once)
     if (d->plan_only) return;   // the tiling alone (a rank of the section-sharded evaluation asks for its range, sharding.py)
     h->qa.assign(d->quad_A, d->quad_A + h->qa_n);
     h->qw.assign(d->quad_w, d->quad_w + h->qw_n);
@@ -648,7 +433,7 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
     h->r_ocp.assign(Q.num_ocp_x, 0.0);
     h->W_ocp.assign(Q.num_ocp_c, 1.0);
     if (const char* env = std::getenv("PYCOLLO_AMD_SPIN_US")) h->spin_us = std::atoi(env);
-    h->n_launches = (int)Q.ph.size() + 1;   // refined after the module is loaded (resident tail: one launch)
+    h->n_launches = pcl::launches_per_evaluation(*h, h->have, Q.ph.size());   // again once the module is loaded
     if (h->device < 0) return;  // structure-only handle
 
     // ---- device side ----------------------------------------------------------------------------
@@ -673,23 +458,24 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
         h->more_modules.push_back(m);
       }
     }
-    HIP_OK(find_fn(h.get(), &h->tail_fn, d->tail_kernel));
-    if (find_fn(h.get(), &h->tail_big_fn, (std::string(d->tail_kernel) + "_big").c_str()) != hipSuccess)
-      h->tail_big_fn = nullptr;
-    if (Q.ph.size() > 1) {
-      if (!kn.merge || find_fn(h.get(), &h->bulk_all_fn, "pc_bulk_all") != hipSuccess) h->bulk_all_fn = nullptr;
-      if (h->bulk_all_fn) {
-        h->d_phase_args.alloc(Q.ph.size() * sizeof(PcPhaseArgs));
-        h->n_launches = 2;
-        if (find_fn(h.get(), &h->bulk_all_res_fn, "pc_bulk_all_r") != hipSuccess) h->bulk_all_res_fn = nullptr;
-        if (h->bulk_all_res_fn && h->wpt_all > 1) {   // the same launch with the replica index compiled in
-          hipFunction_t fw = nullptr;
-          if (find_fn(h.get(), &fw, ("pc_bulk_all_r_w" + std::to_string(h->wpt_all)).c_str()) == hipSuccess && fw)
-            h->bulk_all_res_fn = fw;
-          else
-            (void)hipGetLastError();
-        }
+    // the kernels, by their names in pc_eval_launch.hpp; a code object without an optional one falls back (pcl::Have)
+    auto name = [&](pcl::Kernel k, int phase, int wpt) { return pcl::kernel_name(Q, d->tail_kernel, k, phase, wpt); };
+    auto optional = [&](pcl::Kernel k, int wpt) {
+      if (find_fn(h.get(), &h->fn[k], name(k, 0, wpt).c_str()) != hipSuccess) {
+        (void)hipGetLastError();
+        h->fn[k] = nullptr;
       }
+      return h->have.k[k] = h->fn[k] != nullptr;
+    };
+    HIP_OK(find_fn(h.get(), &h->fn[pcl::TAIL], name(pcl::TAIL, 0, 1).c_str()));
+    optional(pcl::TAIL_BIG, 1);
+    if (Q.ph.size() > 1) {
+      if (kn.merge && optional(pcl::BULK_ALL, 1)) {
+        h->d_phase_args.alloc(Q.ph.size() * sizeof(PcPhaseArgs));
+        if (optional(pcl::BULK_ALL_RES, 1) && h->wpt_all > 1) optional(pcl::BULK_ALL_RES_W, h->wpt_all);
+      }
+    } else if (optional(pcl::BULK_RES, 1) && h->ph[0].wpt > 1) {
+      optional(pcl::BULK_RES_W, h->ph[0].wpt);   // the same kernel with the replica index compiled in (codegen: light / medium models)
     }
     {   // one buffer: the weight tables right behind the A tables (the kernels address both from `qa`)
       std::vector<double> both(h->qa);
@@ -699,16 +485,7 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
     for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
       auto& P = Q.ph[ip];
       auto& D = *h->pd[ip];
-      HIP_OK(find_fn(h.get(), &D.fn, P.bulk_kernel.c_str()));
-      if (Q.ph.size() == 1 && find_fn(h.get(), &D.fn_res, (P.bulk_kernel + "_r").c_str()) != hipSuccess)
-        D.fn_res = nullptr;   // code object without the resident-tail variant: two launches per evaluation
-      if (D.fn_res && D.wpt > 1) {   // the same kernel with the replica index compiled in (codegen: light / medium models)
-        hipFunction_t fw = nullptr;
-        if (find_fn(h.get(), &fw, (P.bulk_kernel + "_r_w" + std::to_string(D.wpt)).c_str()) == hipSuccess && fw)
-          D.fn_res = fw;
-        else
-          (void)hipGetLastError();
-      }
+      HIP_OK(find_fn(h.get(), &D.fn, name(pcl::BULK, (int)ip, 1).c_str()));
       D.tile_k0.upload(P.tile_k0);
       {
         std::vector<int32_t> tn(P.tile_k0.size());
@@ -722,8 +499,8 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
       D.hslotN.upload(P.hslotN);
       D.hsum_slot.upload(P.hsum_slot);
       D.hsum_local.upload(P.hsum_local);
-      D.partials.alloc((size_t)std::max(1, P.nred) * D.n_tiles);
-      D.gran.upload(std::vector<unsigned long long>((size_t)2 * std::max(1, P.nred) * D.n_tiles, 0ull));   // tag 0: never written
+      D.partials.alloc((size_t)std::max(1, P.nred) * h->ph[ip].n_tiles);
+      D.gran.upload(std::vector<unsigned long long>((size_t)2 * std::max(1, P.nred) * h->ph[ip].n_tiles, 0ull));   // tag 0: never written
     }
     {   // the edge records (Shape::rec_slot): never an empty buffer
       std::vector<int64_t> rec_slot(h->rec_slot);
@@ -751,7 +528,7 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
     HIP_OK(hipEventCreateWithFlags(&h->ev_small, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&h->ev_G, hipEventDisableTiming));
     if (const char* env = std::getenv("PYCOLLO_AMD_HOST_MODE")) h->host_mode = std::atoi(env) & 3;
-    if (has_resident_kernel(h.get())) h->n_launches = 1;
+    h->n_launches = pcl::launches_per_evaluation(*h, h->have, Q.ph.size());
   });
   if (!ok) return 0;
   *out = h.release();
@@ -783,14 +560,14 @@ int pc_get_info(const pc_handle* h, pc_info* info) {
     info->nnz_hess = (int64_t)Q.h_row.size();
     info->algorithmic_bytes = 8 * (Q.num_x + Q.num_c) + 8 * (Q.num_c + info->nnz_jac + info->nnz_hess);
     int nt = 0;
-    for (auto& D : h->pd) nt += D->n_tiles;
+    for (auto& D : h->ph) nt += D.n_tiles;
     info->n_tiles_total = nt;
     info->threads_per_block = h->TB;
     info->lds_bytes_max = (h->Q.ph.size() > 1 && h->lds_all > 0) ? h->lds_all : h->lds_max;   // the merged launch's when there is one
     info->n_launches = h->n_launches;
     info->waves_per_tile = 1;
-    for (auto& D : h->pd) info->waves_per_tile = std::max(info->waves_per_tile, (int32_t)D->wpt);
-    if (h->bulk_all_fn) info->waves_per_tile = h->wpt_all;
+    for (auto& D : h->ph) info->waves_per_tile = std::max(info->waves_per_tile, (int32_t)D.wpt);
+    if (h->have.k[pcl::BULK_ALL]) info->waves_per_tile = h->wpt_all;
     info->last_launch = h->last_launch;
   });
 }
@@ -832,11 +609,10 @@ int pc_set_scaling(pc_handle* h, const double* V, const double* r, const double*
     h->V_ocp.assign(V, V + h->Q.num_ocp_x);
     h->r_ocp.assign(r, r + h->Q.num_ocp_x);
     h->W_ocp.assign(W, W + h->Q.num_ocp_c);
-    h->w_J = w_J;
+    h->scal.wJ = w_J;
     upload_scaling(h);
     h->scaling_set = true;
-    h->args_dirty = true;
-    h->host_args_dirty = true;
+    invalidate_blocks(h);
   });
 }
 
@@ -847,8 +623,9 @@ int pc_eval_all_device(pc_handle* h, const double* d_x, double obj_factor, const
     h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     check_timeout(h);   // a previous device-API evaluation whose tail gave up: say so before queueing more work
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    launch_all(h, d_x, d_lambda, d_g, d_jac, d_hess, h->d_out.p + h->o_f, nullptr, PC_FLAG_C | PC_FLAG_G | PC_FLAG_H, st,
-               obj_factor);
+    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
+    call.sigma = obj_factor;
+    launch_all(h, call, st);
   });
 }
 
@@ -865,8 +642,9 @@ int pc_launch_bulk_device(pc_handle* h, const double* d_x, const double* d_lambd
     require_device(h);
     h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    launch_all(h, d_x, d_lambda, d_g, d_jac, d_hess, h->d_out.p + h->o_f, nullptr, PC_FLAG_C | PC_FLAG_G | PC_FLAG_H, st, 1.0,
-               true, false);
+    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
+    call.tail = false;
+    launch_all(h, call, st);
   });
 }
 
@@ -877,7 +655,10 @@ int pc_launch_bulk_flags_device(pc_handle* h, const double* d_x, const double* d
     h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     if (flags & ~(PC_FLAG_C | PC_FLAG_G | PC_FLAG_H)) throw std::runtime_error("flags must be a combination of 1 (g), 2 (jac_g), 4 (hess)");
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    launch_all(h, d_x, d_lambda, d_g, d_jac, d_hess, h->d_out.p + h->o_f, nullptr, flags, st, 1.0, true, false);
+    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
+    call.flags = flags;
+    call.tail = false;
+    launch_all(h, call, st);
   });
 }
 
@@ -887,8 +668,10 @@ int pc_launch_tail_device(pc_handle* h, const double* d_x, double obj_factor, co
     require_device(h);
     h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    launch_all(h, d_x, d_lambda, d_g, d_jac, d_hess, h->d_out.p + h->o_f, nullptr, PC_FLAG_C | PC_FLAG_G | PC_FLAG_H, st,
-               obj_factor, false, true);
+    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
+    call.sigma = obj_factor;
+    call.bulk = false;
+    launch_all(h, call, st);
   });
 }
 
@@ -902,8 +685,11 @@ int pc_launch_tail_objective_device(pc_handle* h, const double* d_x, double obj_
     auto& Q = h->Q;
     h->fc_valid = h->small_synced = h->G_synced = false;
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    launch_all(h, d_x, d_lambda, d_g, d_jac, d_hess, h->d_out.p + h->o_f, h->d_out.p + h->o_gn,
-               PC_FLAG_C | PC_FLAG_G | PC_FLAG_H, st, obj_factor, false, true);
+    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
+    call.grad_nz = h->d_out.p + h->o_gn;
+    call.sigma = obj_factor;
+    call.bulk = false;
+    launch_all(h, call, st);
     HIP_OK(hipMemcpyAsync(h->h_out.p, h->d_out.p, (1 + Q.jgrad_col.size()) * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     if (f) *f = h->h_out.p[h->o_f];
@@ -917,17 +703,15 @@ int pc_launch_tail_objective_device(pc_handle* h, const double* d_x, double obj_
 int pc_set_tile_range(pc_handle* h, int phase, int tile_begin, int tile_end) {
   return guarded(g_err, [&] {
     if (!h || phase < 0 || phase >= (int)h->pd.size()) throw std::runtime_error("phase out of range");
-    auto& D = *h->pd[phase];
-    if (tile_begin < 0 || tile_end < tile_begin || tile_end > D.n_tiles) throw std::runtime_error("tile range out of range");
+    if (tile_begin < 0 || tile_end < tile_begin || tile_end > h->ph[phase].n_tiles) throw std::runtime_error("tile range out of range");
     if (h->device >= 0) {
       HIP_OK(hipSetDevice(h->device));
       HIP_OK(hipDeviceSynchronize());   // launches in flight on any stream still use the old range
     }
-    D.tile_begin = tile_begin;
-    D.tile_end = tile_end;
+    h->rg[phase].tile_begin = tile_begin;
+    h->rg[phase].tile_end = tile_end;
     h->fc_valid = false;
-    h->args_dirty = true;
-    h->host_args_dirty = true;
+    invalidate_blocks(h);
   });
 }
 
@@ -956,9 +740,8 @@ int pc_set_partials_buffer(pc_handle* h, int phase, double* d_partials) {
       HIP_OK(hipSetDevice(h->device));
       HIP_OK(hipDeviceSynchronize());
     }
-    h->pd[phase]->partials_ext = d_partials;
-    h->args_dirty = true;
-    h->host_args_dirty = true;
+    h->rg[phase].partials_ext = d_partials;
+    invalidate_blocks(h);
   });
 }
 
@@ -973,8 +756,9 @@ int pc_eval_all(pc_handle* h, const double* x, double obj_factor, const double* 
     if (lambda != h->h_in.p + h->o_lam) std::memcpy(h->h_in.p + h->o_lam, lambda, Q.num_c * sizeof(double));
     if (!(h->host_mode & 1))
       HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in.p, h->in_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    launch_all(h, kx(h), klam(h), kout(h, h->o_c), kout(h, h->o_G), kout(h, h->o_H), kout(h, h->o_f), kout(h, h->o_gn),
-               PC_FLAG_C | PC_FLAG_G | PC_FLAG_H, h->stream, obj_factor);
+    pcl::Call call = host_call(h, PC_FLAG_C | PC_FLAG_G | PC_FLAG_H);
+    call.sigma = obj_factor;
+    launch_all(h, call, h->stream);
     // one block down: [J | grad J | c~ | G~ | H~]
     copy_down(h, 0, h->o_H + Q.h_row.size());
     wait_stream(h);
@@ -1021,8 +805,7 @@ static void ensure_fcG(pc_handle* h, const double* x, int new_x) {
   require_device(h);
   stage_x(h, x, new_x);
   if (h->fc_valid) return;
-  launch_all(h, kx(h), nullptr, kout(h, h->o_c), kout(h, h->o_G), nullptr, kout(h, h->o_f), kout(h, h->o_gn),
-             PC_FLAG_C | PC_FLAG_G, h->stream, 1.0);
+  launch_all(h, host_call(h, PC_FLAG_C | PC_FLAG_G), h->stream);
   copy_down(h, 0, h->o_c + h->Q.num_c);
   HIP_OK(hipEventRecord(h->ev_small, h->stream));
   h->G_copied = h->prefetch_jac || (h->host_mode & 2);
@@ -1103,8 +886,10 @@ int pc_eval_h(pc_handle* h, const double* x, int new_x, double obj_factor, const
     auto& Q = h->Q;
     stage_x(h, x, new_x);
     stage_lambda(h, lambda);
-    launch_all(h, kx(h), klam(h), nullptr, nullptr, kout(h, h->o_H), kout(h, h->o_f), nullptr, PC_FLAG_H, h->stream,
-               obj_factor);
+    pcl::Call call = host_call(h, PC_FLAG_H);
+    call.grad_nz = nullptr;
+    call.sigma = obj_factor;
+    launch_all(h, call, h->stream);
     copy_down(h, h->o_H, h->o_H + Q.h_row.size());
     wait_stream(h);
     // the stream has drained: earlier copies are complete too -- G~'s only if it was ever issued (prefetch off and
@@ -1128,8 +913,9 @@ int pc_eval_resident(pc_handle* h, const double* x, double obj_factor, const dou
       if (lambda) std::memcpy(h->h_in.p + h->o_lam, lambda, Q.num_c * sizeof(double));
       HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in.p, (lambda ? h->in_total : (size_t)Q.num_x) * sizeof(double),
                             hipMemcpyHostToDevice, h->stream));
-      launch_all(h, kx(h), lambda ? klam(h) : nullptr, kout(h, h->o_c), kout(h, h->o_G), lambda ? kout(h, h->o_H) : nullptr,
-                 kout(h, h->o_f), kout(h, h->o_gn), PC_FLAG_C | PC_FLAG_G | (lambda ? PC_FLAG_H : 0), h->stream, obj_factor);
+      pcl::Call call = host_call(h, PC_FLAG_C | PC_FLAG_G | (lambda ? PC_FLAG_H : 0));
+      call.sigma = obj_factor;
+      launch_all(h, call, h->stream);
       copy_down(h, 0, h->o_c + Q.num_c);
       wait_stream(h);
     } catch (...) {

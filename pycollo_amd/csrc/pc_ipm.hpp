@@ -290,8 +290,11 @@ void ipm_eval_point(pc_ipm* s, const double* d_v, double* d_c_scaled, bool with_
   pc_handle* h = s->h;
   hipStream_t st = h->stream;
   h->fc_valid = h->small_synced = h->G_synced = false;
-  launch_all(h, d_v, nullptr, h->d_out.p + h->o_c, h->d_out.p + h->o_G, nullptr, s->ft.p, with_jac ? s->gradnz.p : nullptr,
-             with_jac ? (PC_FLAG_C | PC_FLAG_G) : PC_FLAG_C, st, 1.0);
+  pcl::Call call = device_call(h, d_v, nullptr, h->d_out.p + h->o_c, h->d_out.p + h->o_G, nullptr);
+  call.fobj = s->ft.p;
+  call.grad_nz = with_jac ? s->gradnz.p : nullptr;
+  call.flags = with_jac ? (PC_FLAG_C | PC_FLAG_G) : PC_FLAG_C;
+  launch_all(h, call, st);
   hipLaunchKernelGGL(ipm_scale_c, dim3(ipm_grid(s->m)), dim3(256), 0, st, h->d_out.p + h->o_c, s->sc.p, s->rhs_c.p, s->slack_of_row.p, d_v,
                      s->n, d_c_scaled, s->m);
   if (with_jac) {
@@ -449,7 +452,11 @@ int pc_ipm_newton(pc_ipm* s, double mu, double tau, double dw_last, double* out8
     const unsigned gu = ipm_grid(s->nu);
     hipLaunchKernelGGL(ipm_mul, dim3(ipm_grid(s->m)), dim3(256), 0, st, s->sc.p, s->lam.p, s->lams.p, s->m);
     h->fc_valid = h->small_synced = h->G_synced = false;
-    launch_all(h, s->v.p, s->lams.p, h->d_out.p + h->o_c, h->d_out.p + h->o_G, h->d_out.p + h->o_H, s->ft.p + 1, nullptr, PC_FLAG_H, st, s->sf);
+    pcl::Call call = device_call(h, s->v.p, s->lams.p, h->d_out.p + h->o_c, h->d_out.p + h->o_G, h->d_out.p + h->o_H);
+    call.fobj = s->ft.p + 1;
+    call.flags = PC_FLAG_H;
+    call.sigma = s->sf;
+    launch_all(h, call, st);
     hipLaunchKernelGGL(ipm_newton_setup, dim3(gu), dim3(256), 0, st, s->v.p, s->vl.p, s->vu.p, s->zl.p, s->zu.p, s->hasl.p, s->hasu.p,
                        s->fixed.p, s->g.p, s->jtl.p, s->c.p, mu, s->Sigma.p, s->gphi.p, s->rhs.p, s->nv, s->m);
     double dw = 0.0, dc = 0.0;

@@ -584,8 +584,8 @@ __device__ __forceinline__ void bulk(const PcPhaseArgs& KA, bool MULTI = false, 
     const int wa = LD->wa, wb = LD->wb;
     A.xz = LD->xz; A.lamd = LD->lamd; A.qa = LD->qa; A.sec_h = LD->sec_h; A.N = LD->N; A.K = LD->K;
     A.tile_begin = LD->tile_begin; A.n_blocks = LD->n_blocks;
-    A.flags = wa & 0xff; A.wpt = (wa >> 8) & 0xf; A.block_threads = ((wa >> 12) & 0xf) << 6; A.spt = (wa >> 16) & 0xfff;
-    A.qa0 = wb & 0xffff; A.qwabs = wb >> 16;
+    A.flags = pc_wa_flags(wa); A.wpt = pc_wa_wpt(wa); A.block_threads = pc_wa_block_threads(wa); A.spt = pc_wa_spt(wa);
+    A.qa0 = pc_wb_qa_off(wb); A.qwabs = pc_wb_qw_abs(wb);
   } else {
     A.x = MULTI ? mx : KA.x; A.lam = MULTI ? mlam : KA.lam; A.x_off = KA.x_off; A.c_off = KA.c_off; A.N = KA.N; A.K = KA.K;
     A.xz = A.x + A.x_off; A.lamd = A.lam + A.c_off; A.qa = KA.qa; A.sec_h = KA.sec_h;

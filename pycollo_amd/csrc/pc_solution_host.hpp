@@ -129,12 +129,12 @@ void solution_costate(pc_solution* s, const double* d_lam, int n_orders, const i
   d_A.upload(std::vector<double>(tabA, tabA + a_total));
   for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
     auto& P = Q.ph[ip];
-    auto& D = *h->pd[ip];
+    const std::vector<double>& scal = h->scal.phase[ip];
     auto& S = *s->ph[ip];
     const pcs::FitPlan& F = S.plan;
     const pcs::CostatePlan C =
         pcs::build_costate_plan(F, n_orders, orders, P.n_y, P.n_q, P.c_off, P.c_int_off, Q.num_c, h->lds_limit);
-    if (D.scal_host.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
+    if (scal.size() > PC_MAX_SCAL) throw std::runtime_error("too many scaling constants for the kernel argument block");
     const size_t ny = (size_t)std::max(1, P.n_y);
     if (!S.node_p.p) {
       S.node_p.alloc(ny * F.N);
@@ -150,8 +150,8 @@ void solution_costate(pc_solution* s, const double* d_lam, int n_orders, const i
     // the variables are unscaled as the solution's node values were (the view of creation); the rows are scaled as of
     // now: the multipliers belong to the constraint scaling the handle holds when they are set (scal's tail: Wd Wp Wi)
     a.v = S.view;
-    const size_t o_w = D.scal_host.size() - (size_t)(P.n_y + P.n_p + P.n_q);
-    for (size_t i = o_w; i < D.scal_host.size(); ++i) a.v.scal[i] = D.scal_host[i];
+    const size_t o_w = scal.size() - (size_t)(P.n_y + P.n_p + P.n_q);
+    for (size_t i = o_w; i < scal.size(); ++i) a.v.scal[i] = scal[i];
     a.lam = d_lam;
     a.tile_k0 = S.tile_k0.p;
     a.lane0 = S.lane0.p;
@@ -164,7 +164,7 @@ void solution_costate(pc_solution* s, const double* d_lam, int n_orders, const i
     a.nu = S.nu.p;
     a.c_off = P.c_off;
     a.c_int_off = P.c_int_off;
-    a.wJ = h->w_J;
+    a.wJ = h->scal.wJ;
     a.NC = F.NC;
     a.tab_total = F.tab_total;
     a.a_total = a_total;
@@ -181,7 +181,7 @@ int solution_set_multipliers(pc_solution* s, const double* lam, int64_t n_lam, b
   return guarded(g_err, [&] {
     if (!s) throw std::runtime_error("null solution");
     require_device(s->h);
-    pcs::check_multiplier_args(lam, n_lam, s->h->Q.num_c, tabA, s->h->w_J);
+    pcs::check_multiplier_args(lam, n_lam, s->h->Q.num_c, tabA, s->h->scal.wJ);
     HIP_OK(hipSetDevice(s->h->device));
     const double* d_lam = lam;
     if (!on_device) {

@@ -69,6 +69,18 @@ class _Info(C.Structure):
                 ("last_launch", C.c_int32)]
 
 
+# the fields of pc_info.last_launch: include/pycollo_amd.h's PC_LAUNCH_* (tests/test_eval_launch_cpu.py holds them to its text)
+PC_LAUNCH = dict(RESIDENT=1, TAIL_BIG=2, MERGED=4, TAIL_BLOCKS_SHIFT=4, TAIL_BLOCKS_MASK=7, TAIL_WAVES_SHIFT=8,
+                 TAIL_WAVES_MASK=15)
+
+
+def decode_last_launch(ll: int) -> dict:
+    L = PC_LAUNCH
+    return dict(resident=bool(ll & L["RESIDENT"]), tail_big=bool(ll & L["TAIL_BIG"]), merged=bool(ll & L["MERGED"]),
+                tail_blocks=(ll >> L["TAIL_BLOCKS_SHIFT"]) & L["TAIL_BLOCKS_MASK"],
+                tail_block_threads=64 * ((ll >> L["TAIL_WAVES_SHIFT"]) & L["TAIL_WAVES_MASK"]))
+
+
 class _DerivEntry(C.Structure):
     _fields_ = [("kind", C.c_int32), ("located", C.c_int32), ("index", C.c_int64), ("row", C.c_int64), ("col", C.c_int64),
                 ("analytic", C.c_double), ("fd", C.c_double), ("err", C.c_double)]
@@ -434,8 +446,7 @@ class NlpEngine:
         self._check(self._lib.pc_get_info(self._h, C.byref(info)))
         out = {k: getattr(info, k) for k, _ in _Info._fields_}
         ll = out["last_launch"]
-        out.update(resident=bool(ll & 1), tail_big=bool(ll & 2), merged=bool(ll & 4), tail_blocks=(ll >> 4) & 7,
-                   tail_block_threads=64 * ((ll >> 8) & 15))
+        out.update(decode_last_launch(ll))
         return out
 
     def close(self):
