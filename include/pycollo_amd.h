@@ -215,6 +215,11 @@ int pc_set_host_mode(pc_handle* h, int mode);
  * next; 0: jac_g stays in device memory until pc_eval_jac_g is called (a solver whose linear algebra runs on the
  * GPU, pc_kkt_*, never asks) */
 int pc_set_prefetch_jac(pc_handle* h, int on);
+/* A counter that moves whenever the handle stages a point for the pc_eval_f / grad_f / g / jac_g / h callbacks, fills
+ * their cache or invalidates any of it (another entry point, a device-pointer launch, new scaling ...).  A caller
+ * without IPOPT's new_x flag notes the point and this value after a call with new_x = 1 and may pass new_x = 0 at that
+ * point for as long as the value has not moved (NlpEngine.cache_holds).  0 for a null handle. */
+uint64_t pc_cache_generation(const pc_handle* h);
 /* same with every vector resident in device memory; asynchronous on `stream` (hipStream_t, NULL =
  * the handle's stream).  No host synchronisation is performed.
  * AT MOST ONE evaluation per handle may be in flight: a handle owns one set of hand-over buffers (per-tile partial

@@ -2,7 +2,6 @@
 // See include/pycollo_amd.h for the contract and the reference interfaces each entry point replaces.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +18,7 @@
 #include "pc_desc.hpp"
 #include "pc_eval_shape.hpp"
 #include "pc_eval_launch.hpp"
+#include "pc_callback_cache.hpp"
 #include "pc_deriv.hpp"
 #include "pc_solution_plan.hpp"
 
@@ -114,15 +114,8 @@ struct pc_handle : pce::Shape {   // the launch shape pc_create decided (pc_eval
   // up, one copy down
   DevBuf<double> d_in, d_out;
   PinBuf<double> h_in, h_out;
-  // bit 0: the kernels read x~ / lambda straight from the pinned host block (no copy up);
-  // bit 1: the kernels write their outputs straight into the pinned host block (no copy down)
-  int host_mode = 0;
+  pcc::Cache cache;   // what the blocks hold for the host-pointer callbacks, the host mode and the prefetch setting
   hipEvent_t ev_small = nullptr, ev_G = nullptr;               // completion of [J | grad | c~] and of G~ at the cached x
-  bool x_valid = false;      // the staged x~ is the caller's current point
-  bool fc_valid = false;     // J, grad J, c~, G~ at that point have been launched (new_x == 0 reuses them)
-  bool small_synced = false, G_synced = false;
-  bool prefetch_jac = true;  // copy G~ down with every new point (IPOPT asks for it next); off: only when eval_jac_g asks
-  bool G_copied = false;
   DevBuf<int64_t> d_point_x, d_tail_owned, d_pt_hslot, d_g_indptr;
   DevBuf<int32_t> d_pt_hlocal;
   // resident tail (pc_kernels.hpp, RES): one launch per evaluation, the tail runs as block 0 beside the tiles
@@ -207,8 +200,11 @@ hipFunction_t kernel_of(const pc_handle* h, const pcl::Launch& l) {
   return l.kernel == pcl::BULK ? h->pd[l.phase]->fn : h->fn[l.kernel];
 }
 
-// One evaluation, or its tiles' or its tail's part: refresh what a change invalidated, plan the call, launch.
-void launch_all(pc_handle* h, const pcl::Call& call, hipStream_t st) {
+// One evaluation, or its tiles' or its tail's part: refresh what a change invalidated, plan the call, launch.  The one
+// launch site: a call that is not the callback cache's `own` and writes into the handle's result block invalidates it.
+void launch_all(pc_handle* h, const pcl::Call& call, hipStream_t st, bool own = false) {
+  const double* const out[5] = {call.c, call.G, call.H, call.fobj, call.grad_nz};
+  pcc::launched(h->cache, own, pcc::writes_result_block(out, h->d_out.p, h->h_out.p, h->out_total));
   if (h->blocks_dirty) refresh_blocks(h);
   const pcl::Plan p = pcl::plan(h->blocks, *h, h->have, call);
   for (int i = 0; i < p.n; ++i)
@@ -218,6 +214,7 @@ void launch_all(pc_handle* h, const pcl::Call& call, hipStream_t st) {
 
 void upload_scaling(pc_handle* h) {
   auto& Q = h->Q;
+  pcc::input_overwritten(h->cache);   // (first: an upload that fails half-way leaves nothing to reuse either)
   for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
     auto& P = Q.ph[ip];
     auto& D = *h->pd[ip];
@@ -270,7 +267,6 @@ void upload_scaling(pc_handle* h) {
     h->scal.pointr = pr;
     h->scal.Wend = we;
   }
-  h->x_valid = h->fc_valid = false;
 }
 
 void require_device(pc_handle* h) {
@@ -293,25 +289,15 @@ void check_timeout(pc_handle* h) {
   }
 }
 
-// Wait for the handle's stream.  A blocking wait costs an interrupt and a wake-up (~10 us on the MI355X host, a
-// quarter of a 10 k-node callback); the stream is polled for `spin_us` first, which is where a callback completes.
+// Wait for the handle's stream (poll_then_block), then hear a tail that gave up.
 void wait_stream(pc_handle* h) {
-  if (h->spin_us > 0) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      const hipError_t e = hipStreamQuery(h->stream);
-      if (e == hipSuccess) { check_timeout(h); return; }
-      if (e != hipErrorNotReady) HIP_OK(e);
-      if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > h->spin_us) break;
-    }
-  }
-  HIP_OK(hipStreamSynchronize(h->stream));
+  wait_for(h->stream, h->spin_us);
   check_timeout(h);
 }
 // what the kernels are handed for x~, lambda and the outputs: the device mirror, or the pinned host block itself
-const double* kx(pc_handle* h) { return (h->host_mode & 1) ? h->h_in.p : h->d_in.p; }
+const double* kx(pc_handle* h) { return (h->cache.mode & 1) ? h->h_in.p : h->d_in.p; }
 const double* klam(pc_handle* h) { return kx(h) + h->o_lam; }
-double* kout(pc_handle* h, size_t off) { return ((h->host_mode & 2) ? h->h_out.p : h->d_out.p) + off; }
+double* kout(pc_handle* h, size_t off) { return ((h->cache.mode & 2) ? h->h_out.p : h->d_out.p) + off; }
 // a device-pointer call: the caller's vectors, J into the handle's own output block; every flag unless the caller says
 pcl::Call device_call(pc_handle* h, const double* d_x, const double* d_lambda, double* d_g, double* d_jac, double* d_hess) {
   pcl::Call call;
@@ -334,29 +320,69 @@ pcl::Call host_call(pc_handle* h, int flags) {
   return call;
 }
 
-// x~ of a callback: staged (and copied up) only when the caller says the point is new
-void stage_x(pc_handle* h, const double* x, int new_x) {
-  if (!new_x && h->x_valid) return;
-  if (!x) throw std::runtime_error("null x");
-  if (x != h->h_in.p) std::memcpy(h->h_in.p, x, h->Q.num_x * sizeof(double));
-  if (!(h->host_mode & 1))
-    HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in.p, h->Q.num_x * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  h->x_valid = true;
-  h->fc_valid = false;
+// [begin, begin + count) of the input block into its pinned copy unless it is there, and up unless the kernels read that
+void stage(pc_handle* h, const double* src, size_t begin, size_t count) {
+  if (!src) throw std::runtime_error(begin ? "null lambda" : "null x");
+  double* dst = h->h_in.p + begin;
+  if (src != dst) std::memcpy(dst, src, count * sizeof(double));
+  if (!(h->cache.mode & 1))
+    HIP_OK(hipMemcpyAsync(h->d_in.p + begin, dst, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
 }
-
-void stage_lambda(pc_handle* h, const double* lambda) {
-  if (!lambda) throw std::runtime_error("null lambda");
-  double* dst = h->h_in.p + h->o_lam;
-  if (lambda != dst) std::memcpy(dst, lambda, h->Q.num_c * sizeof(double));
-  if (!(h->host_mode & 1))
-    HIP_OK(hipMemcpyAsync(h->d_in.p + h->o_lam, dst, h->Q.num_c * sizeof(double), hipMemcpyHostToDevice, h->stream));
-}
+void stage_x(pc_handle* h, const double* x) { stage(h, x, 0, h->Q.num_x); }
+void stage_lambda(pc_handle* h, const double* lambda) { stage(h, lambda, h->o_lam, h->Q.num_c); }
 
 void copy_down(pc_handle* h, size_t begin, size_t end) {   // [begin, end) of the output block, device -> pinned host
-  if (h->host_mode & 2) return;                             // the kernels wrote there themselves
+  if (h->cache.mode & 2) return;                            // the kernels wrote there themselves
   HIP_OK(hipMemcpyAsync(h->h_out.p + begin, h->d_out.p + begin, (end - begin) * sizeof(double), hipMemcpyDeviceToHost,
                         h->stream));
+}
+void copy_down(pc_handle* h, size_t begin, size_t end, hipEvent_t done) {
+  copy_down(h, begin, end);
+  HIP_OK(hipEventRecord(done, h->stream));
+}
+
+// the body of a host-pointer call that stages or fills: a failure on the way leaves nothing to reuse
+template <class F>
+void or_forget(pc_handle* h, F&& body) {
+  try {
+    body();
+  } catch (...) {
+    pcc::input_overwritten(h->cache);
+    throw;
+  }
+}
+
+// A host-pointer callback (pc_callback_cache.hpp): stage, fill, queue the copies and wait as the cache says.
+void callback(pc_handle* h, const double* x, int new_x, pcc::Want want) {
+  require_device(h);
+  or_forget(h, [&] {
+    const pcc::Todo t = pcc::callback(h->cache, new_x, want);
+    if (t.stage_x) stage_x(h, x);
+    if (t.launch) launch_all(h, host_call(h, PC_FLAG_C | PC_FLAG_G), h->stream, true);
+    if (t.queue_small) copy_down(h, 0, h->o_c + h->Q.num_c, h->ev_small);
+    if (t.queue_G) copy_down(h, h->o_G, h->o_G + h->Q.g_row.size(), h->ev_G);
+    if (t.wait == pcc::NO_WAIT) return;
+    wait_for(t.wait == pcc::EV_G ? h->ev_G : h->ev_small, h->spin_us);
+    check_timeout(h);
+  });
+}
+
+// a device-pointer entry point: the caller's stream or the handle's, the caller's vectors, the entry's own settings
+template <class Tweak>
+hipStream_t launch_device(pc_handle* h, const double* d_x, const double* d_lambda, double* d_g, double* d_jac, double* d_hess,
+                          void* stream, Tweak&& tweak) {
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
+  tweak(call);
+  launch_all(h, call, st);
+  return st;
+}
+
+// grad J of the pinned result block, scattered from its structural non-zeros
+void scatter_grad(pc_handle* h, double* grad) {
+  const auto& Q = h->Q;
+  std::memset(grad, 0, Q.num_x * sizeof(double));
+  for (size_t e = 0; e < Q.jgrad_col.size(); ++e) grad[Q.point_x[Q.jgrad_col[e]]] = h->h_out.p[h->o_gn + e];
 }
 
 // a kernel of the handle's code object, whichever of its modules holds it
@@ -527,7 +553,7 @@ int pc_create(const pc_problem_desc* d, pc_handle** out) {
     std::memset(h->h_out.p, 0, h->out_total * sizeof(double));
     HIP_OK(hipEventCreateWithFlags(&h->ev_small, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&h->ev_G, hipEventDisableTiming));
-    if (const char* env = std::getenv("PYCOLLO_AMD_HOST_MODE")) h->host_mode = std::atoi(env) & 3;
+    if (const char* env = std::getenv("PYCOLLO_AMD_HOST_MODE")) pcc::set_mode(h->cache, std::atoi(env) & 3);
     h->n_launches = pcl::launches_per_evaluation(*h, h->have, Q.ph.size());
   });
   if (!ok) return 0;
@@ -620,12 +646,8 @@ int pc_eval_all_device(pc_handle* h, const double* d_x, double obj_factor, const
                        double* d_jac, double* d_hess, void* stream) {
   return guarded(g_err, [&] {
     require_device(h);
-    h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     check_timeout(h);   // a previous device-API evaluation whose tail gave up: say so before queueing more work
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
-    call.sigma = obj_factor;
-    launch_all(h, call, st);
+    launch_device(h, d_x, d_lambda, d_g, d_jac, d_hess, stream, [&](pcl::Call& call) { call.sigma = obj_factor; });
   });
 }
 
@@ -640,11 +662,7 @@ int pc_launch_bulk_device(pc_handle* h, const double* d_x, const double* d_lambd
                           double* d_hess, void* stream) {
   return guarded(g_err, [&] {
     require_device(h);
-    h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
-    call.tail = false;
-    launch_all(h, call, st);
+    launch_device(h, d_x, d_lambda, d_g, d_jac, d_hess, stream, [](pcl::Call& call) { call.tail = false; });
   });
 }
 
@@ -652,13 +670,11 @@ int pc_launch_bulk_flags_device(pc_handle* h, const double* d_x, const double* d
                                 double* d_hess, int flags, void* stream) {
   return guarded(g_err, [&] {
     require_device(h);
-    h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
     if (flags & ~(PC_FLAG_C | PC_FLAG_G | PC_FLAG_H)) throw std::runtime_error("flags must be a combination of 1 (g), 2 (jac_g), 4 (hess)");
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
-    call.flags = flags;
-    call.tail = false;
-    launch_all(h, call, st);
+    launch_device(h, d_x, d_lambda, d_g, d_jac, d_hess, stream, [&](pcl::Call& call) {
+      call.flags = flags;
+      call.tail = false;
+    });
   });
 }
 
@@ -666,12 +682,10 @@ int pc_launch_tail_device(pc_handle* h, const double* d_x, double obj_factor, co
                           double* d_jac, double* d_hess, void* stream) {
   return guarded(g_err, [&] {
     require_device(h);
-    h->fc_valid = h->small_synced = h->G_synced = false;   // these launches write the handle's f block: a companion host-pointer call must re-evaluate
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
-    call.sigma = obj_factor;
-    call.bulk = false;
-    launch_all(h, call, st);
+    launch_device(h, d_x, d_lambda, d_g, d_jac, d_hess, stream, [&](pcl::Call& call) {
+      call.sigma = obj_factor;
+      call.bulk = false;
+    });
   });
 }
 
@@ -682,21 +696,15 @@ int pc_launch_tail_objective_device(pc_handle* h, const double* d_x, double obj_
                                     double* d_jac, double* d_hess, void* stream, double* f, double* grad) {
   return guarded(g_err, [&] {
     require_device(h);
-    auto& Q = h->Q;
-    h->fc_valid = h->small_synced = h->G_synced = false;
-    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
-    pcl::Call call = device_call(h, d_x, d_lambda, d_g, d_jac, d_hess);
-    call.grad_nz = h->d_out.p + h->o_gn;
-    call.sigma = obj_factor;
-    call.bulk = false;
-    launch_all(h, call, st);
-    HIP_OK(hipMemcpyAsync(h->h_out.p, h->d_out.p, (1 + Q.jgrad_col.size()) * sizeof(double), hipMemcpyDeviceToHost, st));
+    hipStream_t st = launch_device(h, d_x, d_lambda, d_g, d_jac, d_hess, stream, [&](pcl::Call& call) {
+      call.grad_nz = h->d_out.p + h->o_gn;
+      call.sigma = obj_factor;
+      call.bulk = false;
+    });
+    HIP_OK(hipMemcpyAsync(h->h_out.p, h->d_out.p, (1 + h->Q.jgrad_col.size()) * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     if (f) *f = h->h_out.p[h->o_f];
-    if (grad) {
-      std::memset(grad, 0, Q.num_x * sizeof(double));
-      for (size_t e = 0; e < Q.jgrad_col.size(); ++e) grad[Q.point_x[Q.jgrad_col[e]]] = h->h_out.p[h->o_gn + e];
-    }
+    if (grad) scatter_grad(h, grad);
   });
 }
 
@@ -710,7 +718,7 @@ int pc_set_tile_range(pc_handle* h, int phase, int tile_begin, int tile_end) {
     }
     h->rg[phase].tile_begin = tile_begin;
     h->rg[phase].tile_end = tile_end;
-    h->fc_valid = false;
+    pcc::range_changed(h->cache);
     invalidate_blocks(h);
   });
 }
@@ -751,21 +759,23 @@ int pc_eval_all(pc_handle* h, const double* x, double obj_factor, const double* 
     require_device(h);
     auto& Q = h->Q;
     if (!x || !lambda || !g || !jac || !hess) throw std::runtime_error("null argument");
-    // one block up: [x~ | lambda] (contiguous in the pinned block, gap included)
-    if (x != h->h_in.p) std::memcpy(h->h_in.p, x, Q.num_x * sizeof(double));
-    if (lambda != h->h_in.p + h->o_lam) std::memcpy(h->h_in.p + h->o_lam, lambda, Q.num_c * sizeof(double));
-    if (!(h->host_mode & 1))
-      HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in.p, h->in_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    pcl::Call call = host_call(h, PC_FLAG_C | PC_FLAG_G | PC_FLAG_H);
-    call.sigma = obj_factor;
-    launch_all(h, call, h->stream);
-    // one block down: [J | grad J | c~ | G~ | H~]
-    copy_down(h, 0, h->o_H + Q.h_row.size());
-    wait_stream(h);
+    or_forget(h, [&] {
+      // one block up: [x~ | lambda] (contiguous in the pinned block, gap included)
+      if (x != h->h_in.p) std::memcpy(h->h_in.p, x, Q.num_x * sizeof(double));
+      if (lambda != h->h_in.p + h->o_lam) std::memcpy(h->h_in.p + h->o_lam, lambda, Q.num_c * sizeof(double));
+      if (!(h->cache.mode & 1))
+        HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in.p, h->in_total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      pcl::Call call = host_call(h, PC_FLAG_C | PC_FLAG_G | PC_FLAG_H);
+      call.sigma = obj_factor;
+      launch_all(h, call, h->stream, true);
+      // one block down: [J | grad J | c~ | G~ | H~]
+      copy_down(h, 0, h->o_H + Q.h_row.size());
+      wait_stream(h);
+    });
     if (g != h->h_out.p + h->o_c) std::memcpy(g, h->h_out.p + h->o_c, Q.num_c * sizeof(double));
     if (jac != h->h_out.p + h->o_G) std::memcpy(jac, h->h_out.p + h->o_G, Q.g_row.size() * sizeof(double));
     if (hess != h->h_out.p + h->o_H) std::memcpy(hess, h->h_out.p + h->o_H, Q.h_row.size() * sizeof(double));
-    h->x_valid = h->fc_valid = h->small_synced = h->G_synced = true;
+    pcc::filled_all(h->cache);
   });
 }
 
@@ -783,97 +793,49 @@ int pc_host_buffers(pc_handle* h, double** x, double** lambda, double** g, doubl
 int pc_set_prefetch_jac(pc_handle* h, int on) {
   return guarded(g_err, [&] {
     require_device(h);
-    h->prefetch_jac = on != 0;
+    pcc::set_prefetch(h->cache, on != 0);
   });
 }
+
+uint64_t pc_cache_generation(const pc_handle* h) { return h ? h->cache.generation : 0; }
 
 int pc_set_host_mode(pc_handle* h, int mode) {
   return guarded(g_err, [&] {
     require_device(h);
     if (mode < 0 || mode > 3) throw std::runtime_error("host mode must be 0..3");
     HIP_OK(hipStreamSynchronize(h->stream));
-    h->host_mode = mode;
-    h->x_valid = h->fc_valid = false;
+    pcc::set_mode(h->cache, mode);
   });
 }
 
 // J, grad J, c~ and G~ are produced together by the first callback at a new x and kept for the companion calls
 // (IPOPT evaluates f, grad f, g, jac g at the same x, passing new_x = 1 to the first of them only;
 // pycollo/nlp.py:47-57).  The small results [J | grad J | c~] and the large one, G~, come down as two copies so that
-// eval_f / eval_g of a line-search trial point wait for the small one only.
-static void ensure_fcG(pc_handle* h, const double* x, int new_x) {
-  require_device(h);
-  stage_x(h, x, new_x);
-  if (h->fc_valid) return;
-  launch_all(h, host_call(h, PC_FLAG_C | PC_FLAG_G), h->stream);
-  copy_down(h, 0, h->o_c + h->Q.num_c);
-  HIP_OK(hipEventRecord(h->ev_small, h->stream));
-  h->G_copied = h->prefetch_jac || (h->host_mode & 2);
-  if (h->G_copied) {
-    copy_down(h, h->o_G, h->o_G + h->Q.g_row.size());
-    HIP_OK(hipEventRecord(h->ev_G, h->stream));
-  }
-  h->fc_valid = true;
-  h->small_synced = h->G_synced = false;
-}
-static void wait_small(pc_handle* h) {
-  if (h->small_synced) return;
-  if (h->spin_us > 0) {
-    const auto t0 = std::chrono::steady_clock::now();
-    while (hipEventQuery(h->ev_small) == hipErrorNotReady &&
-           std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() <= h->spin_us) {}
-  }
-  HIP_OK(hipEventSynchronize(h->ev_small));
-  check_timeout(h);
-  h->small_synced = true;
-}
-static void wait_G(pc_handle* h) {
-  if (h->G_synced) return;
-  if (!h->G_copied) {   // G~ stayed on the device until somebody asked for it
-    copy_down(h, h->o_G, h->o_G + h->Q.g_row.size());
-    HIP_OK(hipEventRecord(h->ev_G, h->stream));
-    h->G_copied = true;
-  }
-  if (h->spin_us > 0) {
-    const auto t0 = std::chrono::steady_clock::now();
-    while (hipEventQuery(h->ev_G) == hipErrorNotReady &&
-           std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() <= h->spin_us) {}
-  }
-  HIP_OK(hipEventSynchronize(h->ev_G));
-  check_timeout(h);
-  h->small_synced = h->G_synced = true;
-}
-
+// eval_f / eval_g of a line-search trial point wait for the small one only (callback, pc_callback_cache.hpp).
 int pc_eval_f(pc_handle* h, const double* x, int new_x, double* f) {
   return guarded(g_err, [&] {
-    ensure_fcG(h, x, new_x);
-    wait_small(h);
+    callback(h, x, new_x, pcc::SMALL);
     *f = h->h_out.p[h->o_f];
   });
 }
 
 int pc_eval_grad_f(pc_handle* h, const double* x, int new_x, double* grad) {
   return guarded(g_err, [&] {
-    ensure_fcG(h, x, new_x);
-    wait_small(h);
-    auto& Q = h->Q;
-    std::memset(grad, 0, Q.num_x * sizeof(double));
-    for (size_t e = 0; e < Q.jgrad_col.size(); ++e) grad[Q.point_x[Q.jgrad_col[e]]] = h->h_out.p[h->o_gn + e];
+    callback(h, x, new_x, pcc::SMALL);
+    scatter_grad(h, grad);
   });
 }
 
 int pc_eval_g(pc_handle* h, const double* x, int new_x, double* g) {
   return guarded(g_err, [&] {
-    ensure_fcG(h, x, new_x);
-    wait_small(h);
+    callback(h, x, new_x, pcc::SMALL);
     if (g != h->h_out.p + h->o_c) std::memcpy(g, h->h_out.p + h->o_c, h->Q.num_c * sizeof(double));
   });
 }
 
 int pc_eval_jac_g(pc_handle* h, const double* x, int new_x, double* values) {
   return guarded(g_err, [&] {
-    ensure_fcG(h, x, new_x);
-    wait_G(h);
+    callback(h, x, new_x, pcc::G);
     if (values != h->h_out.p + h->o_G) std::memcpy(values, h->h_out.p + h->o_G, h->Q.g_row.size() * sizeof(double));
   });
 }
@@ -884,18 +846,19 @@ int pc_eval_h(pc_handle* h, const double* x, int new_x, double obj_factor, const
   return guarded(g_err, [&] {
     require_device(h);
     auto& Q = h->Q;
-    stage_x(h, x, new_x);
-    stage_lambda(h, lambda);
-    pcl::Call call = host_call(h, PC_FLAG_H);
-    call.grad_nz = nullptr;
-    call.sigma = obj_factor;
-    launch_all(h, call, h->stream);
-    copy_down(h, h->o_H, h->o_H + Q.h_row.size());
-    wait_stream(h);
-    // the stream has drained: earlier copies are complete too -- G~'s only if it was ever issued (prefetch off and
-    // kernels not writing host memory: G~ is still on the device and wait_G must fetch it)
-    h->small_synced = h->fc_valid;
-    h->G_synced = h->fc_valid && h->G_copied;
+    or_forget(h, [&] {
+      if (pcc::hessian(h->cache, new_x).stage_x) stage_x(h, x);
+      stage_lambda(h, lambda);
+      pcl::Call call = host_call(h, PC_FLAG_H);
+      call.grad_nz = nullptr;
+      call.sigma = obj_factor;
+      launch_all(h, call, h->stream, true);
+      copy_down(h, h->o_H, h->o_H + Q.h_row.size());
+      wait_stream(h);
+    });
+    // the stream has drained: earlier copies are complete too -- G~'s only if it was ever queued (prefetch off and
+    // kernels not writing host memory: G~ is still on the device and pc_eval_jac_g must fetch it)
+    pcc::drained(h->cache);
     if (values != h->h_out.p + h->o_H) std::memcpy(values, h->h_out.p + h->o_H, Q.h_row.size() * sizeof(double));
   });
 }
@@ -906,29 +869,21 @@ int pc_eval_resident(pc_handle* h, const double* x, double obj_factor, const dou
     require_device(h);
     auto& Q = h->Q;
     if (!x) throw std::runtime_error("null x");
-    const int mode = h->host_mode;
-    h->host_mode = 0;   // results stay in (and are read from) the device mirror
-    try {
+    pcc::input_overwritten(h->cache);   // (the callback cache describes the host copies; G~ is not copied)
+    {
+      pcc::ThroughMirror mirror(h->cache);   // results stay in (and are read from) the device mirror
       std::memcpy(h->h_in.p, x, Q.num_x * sizeof(double));
       if (lambda) std::memcpy(h->h_in.p + h->o_lam, lambda, Q.num_c * sizeof(double));
       HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in.p, (lambda ? h->in_total : (size_t)Q.num_x) * sizeof(double),
                             hipMemcpyHostToDevice, h->stream));
       pcl::Call call = host_call(h, PC_FLAG_C | PC_FLAG_G | (lambda ? PC_FLAG_H : 0));
       call.sigma = obj_factor;
-      launch_all(h, call, h->stream);
+      launch_all(h, call, h->stream, true);
       copy_down(h, 0, h->o_c + Q.num_c);
       wait_stream(h);
-    } catch (...) {
-      h->host_mode = mode;
-      throw;
     }
-    h->host_mode = mode;
-    h->x_valid = h->fc_valid = false;   // (the callback cache describes the host copies; G~ was not copied)
     if (f) *f = h->h_out.p[h->o_f];
-    if (grad) {
-      std::memset(grad, 0, Q.num_x * sizeof(double));
-      for (size_t e = 0; e < Q.jgrad_col.size(); ++e) grad[Q.point_x[Q.jgrad_col[e]]] = h->h_out.p[h->o_gn + e];
-    }
+    if (grad) scatter_grad(h, grad);
     if (g) std::memcpy(g, h->h_out.p + h->o_c, Q.num_c * sizeof(double));
   });
 }
@@ -992,28 +947,23 @@ int pc_row_norms_jac(pc_handle* h, const double* x, double* norms) {
   return guarded(g_err, [&] {
     require_device(h);
     // always through the device mirror: the row reduction reads G~ back
-    const int mode = h->host_mode;
-    h->host_mode = 0;
-    h->x_valid = h->fc_valid = false;
-    try {
-      ensure_fcG(h, x, 1);
-    } catch (...) {
-      h->host_mode = mode;
-      throw;
+    pcc::input_overwritten(h->cache);
+    {
+      pcc::ThroughMirror mirror(h->cache);
+      callback(h, x, 1, pcc::NOTHING);
     }
-    h->host_mode = mode;
     const int64_t m = h->Q.num_c;
     const int64_t threads = m * 64;
     const int blocks = (int)((threads + 255) / 256);
-    hipLaunchKernelGGL(row_norms_kernel, dim3(blocks), dim3(256), 0, h->stream, h->d_g_indptr.p, h->d_out.p + h->o_G,
-                       h->d_norms.p, m);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(h->h_norms.p, h->d_norms.p, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
+    or_forget(h, [&] {
+      hipLaunchKernelGGL(row_norms_kernel, dim3(blocks), dim3(256), 0, h->stream, h->d_g_indptr.p, h->d_out.p + h->o_G,
+                         h->d_norms.p, m);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(h->h_norms.p, h->d_norms.p, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIP_OK(hipStreamSynchronize(h->stream));
+    });
     std::memcpy(norms, h->h_norms.p, m * sizeof(double));
-    h->x_valid = h->fc_valid = (mode == 0);   // the cache describes the device mirror only
-    h->small_synced = h->fc_valid;
-    h->G_synced = h->fc_valid && h->G_copied;   // (see pc_eval_h)
+    pcc::row_norms_done(h->cache);
   });
 }
 
@@ -1071,9 +1021,9 @@ int pc_mesh_error(pc_handle* h, int phase, const double* x, int n_orders, const 
     d_rel.alloc(P.K);
     d_abs.alloc((size_t)P.K * std::max(1, P.n_y));
     // (always through the device mirror; the callback cache no longer describes it afterwards)
+    pcc::input_overwritten(h->cache);
     std::memcpy(h->h_in.p, x, Q.num_x * sizeof(double));
     HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in.p, Q.num_x * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    h->x_valid = h->fc_valid = false;
     PcRefineArgs a;
     std::memset(&a, 0, sizeof(a));
     a.v = fill_phase_view(h, phase, h->d_in.p);

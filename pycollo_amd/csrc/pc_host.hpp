@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -55,6 +56,29 @@ struct PinBuf {
   }
   ~PinBuf() { free(); }
 };
+
+// Wait for a stream or an event.  A blocking wait costs an interrupt and a wake-up (~10 us on the MI355X host, a quarter
+// of a 10 k-node callback): `query` is polled for `spin_us` first, which is where a callback completes, then `block`
+// is called.  A query error other than "not ready" is thrown.
+template <class Query, class Block>
+void poll_then_block(Query&& query, Block&& block, int spin_us) {
+  if (spin_us > 0) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+      const hipError_t e = query();
+      if (e == hipSuccess) return;
+      if (e != hipErrorNotReady) HIP_OK(e);
+      if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > spin_us) break;
+    }
+  }
+  HIP_OK(block());
+}
+inline void wait_for(hipStream_t st, int spin_us) {
+  poll_then_block([&] { return hipStreamQuery(st); }, [&] { return hipStreamSynchronize(st); }, spin_us);
+}
+inline void wait_for(hipEvent_t ev, int spin_us) {
+  poll_then_block([&] { return hipEventQuery(ev); }, [&] { return hipEventSynchronize(ev); }, spin_us);
+}
 
 // an exported call's body: 1, or 0 with the exception's text in `err` (the caller's thread-local last-error string)
 template <class F>

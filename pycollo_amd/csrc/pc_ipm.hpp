@@ -289,7 +289,6 @@ void ipm_fetch(pc_ipm* s, int count, double* out) {
 void ipm_eval_point(pc_ipm* s, const double* d_v, double* d_c_scaled, bool with_jac) {
   pc_handle* h = s->h;
   hipStream_t st = h->stream;
-  h->fc_valid = h->small_synced = h->G_synced = false;
   pcl::Call call = device_call(h, d_v, nullptr, h->d_out.p + h->o_c, h->d_out.p + h->o_G, nullptr);
   call.fobj = s->ft.p;
   call.grad_nz = with_jac ? s->gradnz.p : nullptr;
@@ -451,7 +450,6 @@ int pc_ipm_newton(pc_ipm* s, double mu, double tau, double dw_last, double* out8
     hipStream_t st = h->stream;
     const unsigned gu = ipm_grid(s->nu);
     hipLaunchKernelGGL(ipm_mul, dim3(ipm_grid(s->m)), dim3(256), 0, st, s->sc.p, s->lam.p, s->lams.p, s->m);
-    h->fc_valid = h->small_synced = h->G_synced = false;
     pcl::Call call = device_call(h, s->v.p, s->lams.p, h->d_out.p + h->o_c, h->d_out.p + h->o_G, h->d_out.p + h->o_H);
     call.fobj = s->ft.p + 1;
     call.flags = PC_FLAG_H;

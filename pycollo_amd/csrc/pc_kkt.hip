@@ -10,8 +10,6 @@
 // by the tables, two factorisations of the same matrix give the same bits.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-
 #include <cstdint>
 #include <cstdlib>
 #include <cstdio>
@@ -939,16 +937,7 @@ static void stage_down(pc_kkt* k, const double* dev, PinBuf<double>& pin, double
 
 // Wait for the stream by polling first: a blocking wait costs an interrupt and a wake-up (10-20 us on the MI355X host),
 // and an interior-point iteration makes four or five of them (pivot counts, residual norms)
-static void kwait(hipStream_t st) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (;;) {
-    const hipError_t e = hipStreamQuery(st);
-    if (e == hipSuccess) return;
-    if (e != hipErrorNotReady) HIP_OK(e);
-    if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > 2000) break;
-  }
-  HIP_OK(hipStreamSynchronize(st));
-}
+static void kwait(hipStream_t st) { wait_for(st, 2000); }
 
 // the solve chain on the handle's stream, device vectors in natural order (d_rhs is not modified; d_x may alias it)
 // (A HIP graph of this string of ~25 launches -- and of the factorisation's ~15 -- was built and measured in round 4:

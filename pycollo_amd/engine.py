@@ -213,7 +213,10 @@ def load_library() -> C.CDLL:
     lib.pc_host_buffers.argtypes = [vp] + [C.POINTER(vp)] * 5
     lib.pc_set_host_mode.argtypes = [vp, C.c_int]
     lib.pc_set_prefetch_jac.argtypes = [vp, C.c_int]
+    lib.pc_cache_generation.argtypes = [vp]
+    lib.pc_cache_generation.restype = C.c_uint64
     lib.pc_eval_all_device.argtypes = [vp, vp, C.c_double, vp, vp, vp, vp, vp]
+    lib.pc_launch_tail_objective_device.argtypes = [vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp]
     lib.pc_launch_bulk_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.pc_launch_tail_device.argtypes = [vp, vp, C.c_double, vp, vp, vp, vp, vp]
     lib.pc_launch_bulk_flags_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
@@ -270,6 +273,11 @@ def choose_spec_orders(n_k, max_orders: int = 4, min_share: float = 0.05) -> tup
 
 def _ptr(a, typ):
     return a.ctypes.data_as(typ) if a.size else C.cast(None, typ)
+
+
+def _addr(t):
+    """Device address of a torch tensor, or the raw address itself."""
+    return t.data_ptr() if hasattr(t, "data_ptr") else int(t)
 
 
 def interp_linear(tau_prev, vals_prev, tau_new, device: int = 0) -> np.ndarray:
@@ -472,7 +480,6 @@ class NlpEngine:
             raise ValueError(f"V_ocp / r_ocp must have {self.layout.num_ocp_x} entries")
         if self.W_ocp.shape != (self.layout.num_ocp_c,):
             raise ValueError(f"W_ocp must have {self.layout.num_ocp_c} entries")
-        self._cached_x = None
         self._check(self._lib.pc_set_scaling(self._h, self.V_ocp.ctypes.data, self.r_ocp.ctypes.data,
                                              self.W_ocp.ctypes.data, self.w_J))
 
@@ -506,47 +513,46 @@ class NlpEngine:
         return np.lexsort((r, c))
 
     # ---- evaluation (host pointers) ------------------------------------------------------------
-    def _x(self, x, new_x=None):
-        """``new_x``: True / False for the IPOPT-protocol callbacks (the point the library's cache describes is
-        tracked in ``_cached_x``), None for every other entry point, after which no cached point is assumed."""
+    def _x(self, x):
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         if x.shape[0] != self.num_x:
             raise ValueError(f"x must have {self.num_x} entries")
-        if new_x is None:
-            self._cached_x = None
-        elif new_x:
-            self._cached_x = x.copy()
         return x
+
+    def _callback(self, fn, x, new_x, *args):
+        """An IPOPT-protocol callback ``fn(h, x, new_x, ...)``.  After one with ``new_x`` the point and the generation of
+        the library's cache (``pc_cache_generation``) are noted: the library owns the record of what invalidates it."""
+        x = self._x(x)
+        self._check(fn(self._h, x.ctypes.data, int(new_x), *args))
+        if new_x:
+            self._cached = (x.copy(), self._lib.pc_cache_generation(self._h))
 
     def cache_holds(self, x) -> bool:
         """True when the library's J / grad J / c~ / G~ cache was filled at exactly ``x`` by the IPOPT-protocol
         callbacks and nothing else has touched the handle since: the test a caller without IPOPT's ``new_x`` flag
         (cyipopt) needs before it may pass ``new_x = 0``."""
-        c = getattr(self, "_cached_x", None)
-        return c is not None and np.array_equal(np.asarray(x, dtype=np.float64).reshape(-1), c)
+        c = getattr(self, "_cached", None)
+        return (c is not None and c[1] == self._lib.pc_cache_generation(self._h)
+                and np.array_equal(np.asarray(x, dtype=np.float64).reshape(-1), c[0]))
 
     def evaluate_J(self, x, new_x=True):
-        x = self._x(x, bool(new_x))
         out = C.c_double()
-        self._check(self._lib.pc_eval_f(self._h, x.ctypes.data, int(new_x), C.addressof(out)))
+        self._callback(self._lib.pc_eval_f, x, new_x, C.addressof(out))
         return out.value
 
     def evaluate_g(self, x, new_x=True):
-        x = self._x(x, bool(new_x))
         g = np.empty(self.num_x)
-        self._check(self._lib.pc_eval_grad_f(self._h, x.ctypes.data, int(new_x), g.ctypes.data))
+        self._callback(self._lib.pc_eval_grad_f, x, new_x, g.ctypes.data)
         return g
 
     def evaluate_c(self, x, new_x=True):
-        x = self._x(x, bool(new_x))
         c = np.empty(self.num_c)
-        self._check(self._lib.pc_eval_g(self._h, x.ctypes.data, int(new_x), c.ctypes.data))
+        self._callback(self._lib.pc_eval_g, x, new_x, c.ctypes.data)
         return c
 
     def evaluate_G_nonzeros(self, x, new_x=True):
-        x = self._x(x, bool(new_x))
         v = np.empty(self.nnz_jac)
-        self._check(self._lib.pc_eval_jac_g(self._h, x.ctypes.data, int(new_x), v.ctypes.data))
+        self._callback(self._lib.pc_eval_jac_g, x, new_x, v.ctypes.data)
         return v
 
     def evaluate_G(self, x):
@@ -554,13 +560,11 @@ class NlpEngine:
         return sparse.coo_matrix((self.evaluate_G_nonzeros(x), (r, c)), shape=(self.num_c, self.num_x))
 
     def evaluate_H_nonzeros(self, x, obj_factor, lagrange, new_x=True):
-        x = self._x(x, bool(new_x))
         lam = np.ascontiguousarray(lagrange, dtype=np.float64).reshape(-1)
         if lam.shape[0] != self.num_c:
             raise ValueError(f"lagrange must have {self.num_c} entries")
         v = np.empty(self.nnz_hess)
-        self._check(self._lib.pc_eval_h(self._h, x.ctypes.data, int(new_x), float(obj_factor), lam.ctypes.data, 1,
-                                        v.ctypes.data))
+        self._callback(self._lib.pc_eval_h, x, new_x, float(obj_factor), lam.ctypes.data, 1, v.ctypes.data)
         return v
 
     def evaluate_H(self, x, obj_factor, lagrange):
@@ -594,7 +598,6 @@ class NlpEngine:
     def evaluate_all_inplace(self, obj_factor=1.0):
         """Fused c, G, H at the (x~, lambda) already written into :meth:`host_buffers`; results are read there."""
         x, lam, c, g, h = self.host_buffers()
-        self._cached_x = None
         self._check(self._lib.pc_eval_all(self._h, x.ctypes.data, float(obj_factor), lam.ctypes.data, c.ctypes.data,
                                           g.ctypes.data, h.ctypes.data))
         return c, g, h
@@ -602,7 +605,6 @@ class NlpEngine:
     def set_host_mode(self, mode: int):
         """0: one DMA copy up / down; 1: kernels read x~, lambda from pinned host memory; 2: kernels write c~, G~, H~
         to pinned host memory; 3: both (``pc_set_host_mode``)."""
-        self._cached_x = None
         self._check(self._lib.pc_set_host_mode(self._h, int(mode)))
 
     def evaluate_resident(self, x, obj_factor=1.0, lagrange=None, want_grad=True):
@@ -629,62 +631,43 @@ class NlpEngine:
 
     # ---- evaluation (device pointers; torch tensors or raw addresses) ---------------------------
     def evaluate_all_device(self, d_x, obj_factor, d_lam, d_c, d_G, d_H, stream=None):
-        def addr(t):
-            return t.data_ptr() if hasattr(t, "data_ptr") else int(t)
-        self._cached_x = None   # (the launch overwrites the handle's f block)
-        self._check(self._lib.pc_eval_all_device(self._h, addr(d_x), float(obj_factor), addr(d_lam), addr(d_c),
-                                                 addr(d_G), addr(d_H), stream))
+        self._check(self._lib.pc_eval_all_device(self._h, _addr(d_x), float(obj_factor), _addr(d_lam), _addr(d_c),
+                                                 _addr(d_G), _addr(d_H), stream))
 
     def bind_device(self, d_x, d_lam, d_c, d_G, d_H, stream=None):
         """``f(obj_factor)`` = :meth:`evaluate_all_device` on fixed device buffers, with the addresses resolved once.
         At 10 k nodes an evaluation is ~8 us; resolving five ``data_ptr()`` per call is a visible part of that."""
-        def addr(t):
-            return t.data_ptr() if hasattr(t, "data_ptr") else int(t)
         fn, h, err = self._lib.pc_eval_all_device, self._h, self._lib.pc_last_error
-        px, pl, pc, pG, pH = addr(d_x), addr(d_lam), addr(d_c), addr(d_G), addr(d_H)
+        px, pl, pc, pG, pH = _addr(d_x), _addr(d_lam), _addr(d_c), _addr(d_G), _addr(d_H)
         keep = (d_x, d_lam, d_c, d_G, d_H)       # the buffers must outlive the callable
 
         def call(obj_factor=1.0, _keep=keep):
-            self._cached_x = None
             if not fn(h, px, obj_factor, pl, pc, pG, pH, stream):
                 raise RuntimeError("pc_eval_all_device failed: " + err().decode())
         return call
 
     def launch_bulk_only(self, d_x, d_lam, d_c, d_G, d_H, stream=None):
         """Profiling aid: only the bulk kernels of :meth:`evaluate_all_device`."""
-        def addr(t):
-            return t.data_ptr() if hasattr(t, "data_ptr") else int(t)
-        self._cached_x = None   # (the launch overwrites the handle's f block)
-        self._check(self._lib.pc_launch_bulk_device(self._h, addr(d_x), addr(d_lam), addr(d_c), addr(d_G), addr(d_H),
+        self._check(self._lib.pc_launch_bulk_device(self._h, _addr(d_x), _addr(d_lam), _addr(d_c), _addr(d_G), _addr(d_H),
                                                     stream))
 
     def launch_bulk_flags(self, d_x, d_lam, d_c, d_G, d_H, flags: int, stream=None):
         """The tile kernels for a subset of the outputs: ``flags`` = 1 (c~) | 2 (G~) | 4 (H~)."""
-        def addr(t):
-            return t.data_ptr() if hasattr(t, "data_ptr") else int(t)
-        self._cached_x = None   # (the launch overwrites the handle's f block)
-        self._check(self._lib.pc_launch_bulk_flags_device(self._h, addr(d_x), addr(d_lam), addr(d_c), addr(d_G), addr(d_H),
+        self._check(self._lib.pc_launch_bulk_flags_device(self._h, _addr(d_x), _addr(d_lam), _addr(d_c), _addr(d_G), _addr(d_H),
                                                           int(flags), stream))
 
     def launch_tail_only(self, d_x, obj_factor, d_lam, d_c, d_G, d_H, stream=None):
-        def addr(t):
-            return t.data_ptr() if hasattr(t, "data_ptr") else int(t)
-        self._cached_x = None   # (the launch overwrites the handle's f block)
-        self._check(self._lib.pc_launch_tail_device(self._h, addr(d_x), float(obj_factor), addr(d_lam), addr(d_c),
-                                                    addr(d_G), addr(d_H), stream))
+        self._check(self._lib.pc_launch_tail_device(self._h, _addr(d_x), float(obj_factor), _addr(d_lam), _addr(d_c),
+                                                    _addr(d_G), _addr(d_H), stream))
 
 
     def launch_tail_objective(self, d_x, obj_factor, d_lam, d_c, d_G, d_H, stream=None, want_grad=True):
         """``launch_tail_only`` that also returns (J, grad J or None) and synchronises the stream
         (``pc_launch_tail_objective_device``): the objective callbacks of a rank of a sharded solve."""
-        def addr(t):
-            return t.data_ptr() if hasattr(t, "data_ptr") else int(t)
-        self._cached_x = None
         f = C.c_double()
         grad = np.empty(self.num_x) if want_grad else None
-        self._lib.pc_launch_tail_objective_device.argtypes = [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 5 + [C.c_void_p, C.c_void_p]
-        self._check(self._lib.pc_launch_tail_objective_device(self._h, addr(d_x), float(obj_factor), addr(d_lam), addr(d_c), addr(d_G),
-                                                              addr(d_H), stream, C.addressof(f), None if grad is None else grad.ctypes.data))
+        self._check(self._lib.pc_launch_tail_objective_device(self._h, _addr(d_x), float(obj_factor), _addr(d_lam), _addr(d_c), _addr(d_G),
+                                                              _addr(d_H), stream, C.addressof(f), None if grad is None else grad.ctypes.data))
         return f.value, grad
 
     def set_tile_range(self, phase: int, begin: int, end: int):

@@ -259,3 +259,78 @@ def test_device_api_is_unaffected_by_a_mesh_error_in_between(built):
     # ... and the host callbacks after it still describe their own point
     assert_matches_oracle(ora, x1, c=eng.evaluate_c(x1), G=eng.evaluate_G_nonzeros(x1, new_x=False))
     eng.close()
+
+
+def test_cache_generation_follows_the_rules(built):
+    """pc_cache_generation (csrc/pc_callback_cache.hpp) moves exactly when the cache stages a point (+1), is
+    filled (+1) or is invalidated (+1 per event; pc_row_norms_jac is four events), and stays for callbacks served from
+    the cache, pc_set_prefetch_jac and the derivative check; NlpEngine.cache_holds follows it.  A callback with
+    new_x = 0 after each invalidating call returns the bits of the first evaluation at that point."""
+    import torch
+    from pycollo_amd.engine import PycolloGpuProblem
+    from pycollo_amd.iteration import MeshIteration
+    from pycollo_amd.refinement import mesh_error
+    from test_gpu_ipm_steps import _probe_class
+    it = MeshIteration(problems.cart_pole(K=30, order=4), device=0)
+    eng = it.engine
+    # a device-resident interior-point state on the same handle, stopped at its start: its launches write c~, G~ and H~
+    # into the handle's result block (pc_ipm_eval_point, pc_ipm_newton)
+    pobj = PycolloGpuProblem(eng)
+    ipm = _probe_class()(pobj, pobj.n, pobj.m, it.x_bnd_l, it.x_bnd_u, it.c_bnd_l, it.c_bnd_u, tol=1e-8, max_iter=0)
+    assert ipm.solve(it.guess_x_tilde).iterations == 0
+    eng.set_prefetch_jac(True)
+    eng.set_host_mode(0)
+    rng = np.random.default_rng(37)
+    x, other = rng.uniform(-0.4, 0.4, eng.num_x), rng.uniform(-0.4, 0.4, eng.num_x)
+    lam = rng.normal(size=eng.num_c)
+    dev = torch.device("cuda", 0)
+    dx, dl = torch.from_numpy(other).to(dev), torch.from_numpy(lam).to(dev)
+    dc = torch.empty(eng.num_c, dtype=torch.float64, device=dev)
+    dG = torch.empty(eng.nnz_jac, dtype=torch.float64, device=dev)
+    dH = torch.empty(eng.nnz_hess, dtype=torch.float64, device=dev)
+
+    def gen():
+        return eng._lib.pc_cache_generation(eng._h)
+
+    def device_launch():
+        eng.evaluate_all_device(dx, 1.0, dl, dc, dG, dH)
+        eng.synchronize()
+
+    g0 = gen()
+    first = (eng.evaluate_J(x), eng.evaluate_g(x, new_x=False), eng.evaluate_c(x, new_x=False),
+             eng.evaluate_G_nonzeros(x, new_x=False))
+    assert gen() - g0 == 2 and eng.cache_holds(x) and not eng.cache_holds(other)     # staged, filled; companions: nothing
+    H = eng.evaluate_H_nonzeros(x, 0.9, lam, new_x=False)
+    eng.set_prefetch_jac(False)
+    eng.set_prefetch_jac(True)
+    assert eng.check_derivatives(x, 0.9, lam).ok
+    assert gen() - g0 == 2 and eng.cache_holds(x)
+    n_tiles = len(eng.phase_tiles(0)[0]) - 1
+    # (call, generations it moves, generations the new_x = 0 callback after it moves: stage and / or fill)
+    movers = [
+        ("evaluate_all", lambda: eng.evaluate_all(x, 0.9, lam), 1, 0),
+        ("device launch", device_launch, 1, 1),
+        ("interior-point evaluation", ipm._eval_point, 1, 1),
+        ("interior-point evaluation and Newton step", lambda: (ipm._eval_point(), ipm._newton(ipm.mu_init, 0.99, 0.0)), 2, 1),
+        ("mesh_error", lambda: mesh_error(eng, other), 1, 2),
+        ("row norms", lambda: eng.G_row_norms(x), 4, 0),
+        ("resident", lambda: eng.evaluate_resident(other), 1, 2),
+        ("set_scaling", lambda: eng.set_scaling(eng.V_ocp, eng.r_ocp, eng.W_ocp, 1.0), 1, 2),
+        ("set_tile_range", lambda: eng.set_tile_range(0, 0, n_tiles), 1, 1),
+        ("hessian at a new point", lambda: eng.evaluate_H_nonzeros(x, 0.9, lam, new_x=True), 1, 1),
+    ] + [(f"host mode {m}", lambda m=m: eng.set_host_mode(m), 1, 2) for m in (1, 2, 3, 0)]
+    for i, (name, call, moved, refill) in enumerate(movers):
+        eng.evaluate_c(x, new_x=True)
+        assert eng.cache_holds(x), name
+        g1 = gen()
+        call()
+        assert gen() - g1 == moved, name
+        assert eng.cache_holds(x) == (name == "hessian at a new point"), name   # (that call notes the point itself)
+        g1 = gen()
+        again = (eng.evaluate_J, eng.evaluate_g, eng.evaluate_c, eng.evaluate_G_nonzeros)[i % 4](x, new_x=False)
+        np.testing.assert_array_equal(again, first[i % 4], err_msg=name)
+        assert gen() - g1 == refill, name
+        np.testing.assert_array_equal(eng.evaluate_H_nonzeros(x, 0.9, lam, new_x=False), H, err_msg=name)
+        assert gen() - g1 == refill, name
+    ipm.close()
+    eng.close()
