@@ -582,7 +582,8 @@ int pc_solution_sample_device(pc_solution* sol, int phase, const double* d_t, in
  * on the handle's stream and synchronises; may be called again with other multipliers. */
 int pc_solution_set_multipliers(pc_solution* sol, const double* lam, int64_t n_lam, int n_orders, const int32_t* orders,
                                 const double* tabA);
-/* the same from a device vector, read in place */
+/* the same from a device vector (either way the solution keeps a device copy: pc_solution_set_bound_multipliers reads
+ * the path rows from it later) */
 int pc_solution_set_multipliers_device(pc_solution* sol, const double* d_lam, int64_t n_lam, int n_orders, const int32_t* orders,
                                        const double* tabA);
 /* p [n_y][N], H [N], nu [n_q]; NULL: skipped.  These four fail until multipliers were set. */
@@ -595,6 +596,44 @@ int pc_solution_sample_costate(pc_solution* sol, int phase, const double* t, int
 /* the same with device pointers, queued on the handle's stream; does not synchronise */
 int pc_solution_sample_costate_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_p,
                                       double* d_H);
+
+/* ---- path and bound multipliers, the gradients of the augmented Hamiltonian (no reference counterpart) ----
+ * z: zu - zl, the signed multipliers of the n_z = num_x variable bounds of the scaled NLP (the solver's lam_x), or NULL:
+ * no bound multipliers.  With omega_j and w, W as above (the scaling pc_solution_set_multipliers read), V the variable
+ * scaling of the solution and stretch = (tF - t0) / 2:
+ *   mu_i(j)   = Wp_i lam[c_path_off + i N + j] / (w stretch omega_j)
+ *   zeta_b(j) = z[x_off + b N + j] / (w V_b stretch omega_j), b over the n_y states, then the n_u controls; a state's
+ *               entry at nodes 0 and N - 1 belongs to the endpoint bound: zeta is 0 there and z / (w V_b) goes to
+ *               end_z [n_y][2]
+ *   H_z(j)    = sum_a p_a df_a/dz + sum_i mu_i dp_i/dz + sum_m rho nu_m dg_m/dz at the node, z a state or a control;
+ *               rho is the weight the NLP's integral rows give a node over omega_j: 1 under Lobatto, 2 under Radau, whose
+ *               rule weights sum to 2 (H of pc_solution_costate_nodes keeps nu_m alone)
+ * At the Radau phase-final node (omega = 0) mu, zeta of the controls and H_z are NaN.  Between the nodes mu and zeta are
+ * the sections' degree n_k - 1 interpolants (the phase's last section: formed with the ydot table of
+ * pc_solution_create).  Fails until pc_solution_set_multipliers has run; runs pc_sol_multipliers_p<i> once per phase on the
+ * handle's stream and synchronises; may be called again. */
+int pc_solution_set_bound_multipliers(pc_solution* sol, const double* z, int64_t n_z);
+/* the same from a device vector, read in place */
+int pc_solution_set_bound_multipliers_device(pc_solution* sol, const double* d_z, int64_t n_z);
+/* mu [n_p][N], zeta [n_y + n_u][N], end_z [n_y][2], H_y [n_y][N], H_u [n_u][N]; NULL: skipped.  zeta and end_z fail
+ * when no bound multipliers were given.  pc_solution_multiplier_nodes, pc_solution_multiplier_coefficients and the two
+ * pc_solution_sample_optimality calls fail until pc_solution_set_bound_multipliers has run. */
+int pc_solution_multiplier_nodes(pc_solution* sol, int phase, double* mu, double* zeta, double* end_z, double* H_y, double* H_u);
+/* mu_coef [n_p][N + K - 1], zeta_coef [n_y + n_u][N + K - 1] */
+int pc_solution_multiplier_coefficients(pc_solution* sol, int phase, double* mu_coef, double* zeta_coef);
+/* H_y [n_y][n_t], H_u [n_u][n_t], dp = dp/dt [n_y][n_t], mu [n_p][n_t], zeta [n_y + n_u][n_t] (not written when no bound
+ * multipliers were given) at the queries of pc_solution_sample (same flags, same range handling): the gradients at the
+ * interpolated (y(t), u(t)) with p(t), mu(t) and rho nu.  Host pointers; synchronises. */
+int pc_solution_sample_optimality(pc_solution* sol, int phase, const double* t, int64_t n_t, int flags, double* H_y, double* H_u,
+                                  double* dp, double* mu, double* zeta);
+/* the same with device pointers, queued on the handle's stream; does not synchronise */
+int pc_solution_sample_optimality_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_H_y,
+                                         double* d_H_u, double* d_dp, double* d_mu, double* d_zeta);
+
+/* Lam [n_y][N - 1] = W lam / w on the phase's defect rows, from the solution's own copy of the multipliers and the scaling
+ * they were set under: what the discrete defect term D_a(j) of DESIGN 8f is summed from.  Fails until multipliers were
+ * set. */
+int pc_solution_defect_multipliers(pc_solution* sol, int phase, double* Lam);
 
 /* ---- forward propagation under the solution's controls (no reference counterpart) ----
  * seg_nodes [n_seg + 1]: strictly ascending node indices, first 0, last N - 1.  Segment i is one initial-value problem:

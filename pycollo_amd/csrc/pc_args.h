@@ -430,6 +430,53 @@ struct PcSolCostateSampleArgs {
   double* out_H;            // [Q]
 };
 
+// Arguments of the optimality kernels (pc_solution.hpp, "path and bound multipliers").  lam and z are the scaled
+// multiplier vectors of the whole NLP, read in place: path row i of node j is lam[c_path_off + i N + j], the bound
+// multiplier of node variable b is z[v.x_off + b N + j] (z null: no bound multipliers, nothing of zeta is written).
+// tabW holds the last row of every A table (order n's n weights at offW[n]); tabD is the fit kernel's ydot table, with
+// which the phase's last section forms its coefficients.  v.scal's Wp entries and wJ are the scaling lam belongs to.
+// int_scale: the NLP's integral rows weigh integrand m at node j with int_scale omega_j (1 under Lobatto; 2 under Radau,
+// whose rule weights sum to 2 where the last row of A sums to 1), so int_scale nu_m is its weight in H_y and H_u.
+struct PcSolMultiplierArgs {
+  PcPhaseView v;
+  const double* lam;        // [num_c]
+  const double* z;          // [num_x] zu - zl, or null
+  const int32_t* tile_k0;   // [n_tiles+1] the fit kernel's tiles
+  const int32_t* lane0;     // [K]
+  const double* sec_tau;    // [K+1]
+  const double* tabW;       // per order n: the n node weights, A(n)[n - 2][.]
+  const double* tabU;       // per order n: n x n
+  const double* tabD;       // per order n: n x n
+  const double* node_p;     // [NY][N] the costates (pc_sol_costate)
+  const double* nu;         // [NQ]
+  double* node_mu;          // [NP][N]
+  double* node_zeta;        // [NY + NU][N]
+  double* end_z;            // [NY][2] the state bounds' multipliers at nodes 0 and N - 1, without the node weight
+  double* node_Hz;          // [NY + NU][N] gradient of the augmented Hamiltonian
+  double* coef_mu;          // [NP][NC]
+  double* coef_zeta;        // [NY + NU][NC]
+  int64_t c_path_off;
+  double wJ;
+  double int_scale;         // weight of an integrand in the NLP's integral rows over the node weight omega (see below)
+  int32_t NC, tab_total, w_total, reserved;
+  int32_t offC[PC_MAX_ORDER + 1];
+  int32_t offW[PC_MAX_ORDER + 1];
+};
+
+struct PcSolOptimalitySampleArgs {
+  PcSolSampleArgs s;        // the queries, the flags and the trajectory's polynomials (its outputs are not used)
+  const double* coef_p;     // [NY][NC]
+  const double* nu;         // [NQ]
+  const double* coef_mu;    // [NP][NC]
+  const double* coef_zeta;  // [NY + NU][NC] or null
+  double int_scale;         // as in PcSolMultiplierArgs
+  double* out_Hy;           // [NY][Q]
+  double* out_Hu;           // [NU][Q]
+  double* out_dp;           // [NY][Q] dp/dt
+  double* out_mu;           // [NP][Q]
+  double* out_zeta;         // [NY + NU][Q] (not written without coef_zeta)
+};
+
 // Arguments of the forward propagation (pc_solution.hpp, "propagation"): the dynamics integrated under the
 // solution's control interpolant by Dormand-Prince 5(4), one lane per segment of consecutive node intervals.
 #define PC_SOL_PROP_TB 64              // lanes of a workgroup of pc_sol_propagate

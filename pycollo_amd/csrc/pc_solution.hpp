@@ -422,6 +422,193 @@ __device__ __forceinline__ void sol_sample_costate(const PcSolCostateSampleArgs&
 }
 
 // ---------------------------------------------------------------------------------------------
+// Path and bound multipliers, the gradients of the augmented Hamiltonian.  With omega_j the node weight of
+// the costate kernel (same sections, same order of the sum) and den = stretch omega_j:
+//   mu_i(j)   = (Wp_i lam~[c_path_off + i N + j] / w) / den
+//   zeta_b(j) = (z~[x_off + b N + j] / (w V_b)) / den;  a state's entry at nodes 0 and N - 1 is the endpoint bound's: zeta
+//               is 0 there and the value without den goes to end_z [NY][2]
+//   H_z(j)    = sum over the tape's first partials, table order, of mult[jr] Jv on column jc < NZ, mult = [p | mu | rho nu],
+//               rho = int_scale: the integral rows' node weight over omega_j (1 under Lobatto, 2 under Radau)
+// The Radau phase-final node (omega = 0): mu, zeta_u and H_z are NaN, and 0 is staged for the contraction below.
+//
+// pc_sol_multipliers_p<i>: the tiles and lanes of pc_sol_fit.  Lane j of a section then contracts row j of the C_u table
+// (the phase's last section: of the ydot table, whose Radau form leaves the final node out) with the section's staged
+// node values: coefficient j of mu and zeta.  Both lanes of a shared node compute the same values; the section the node
+// opens writes them.
+// ---------------------------------------------------------------------------------------------
+// d/dc of sum_j cf[j] P_j(c), j < n: Clenshaw's recurrence differentiated (u_j' = (2j+1)/(j+1) u_(j+1) + al u_(j+1)' - be u_(j+2)')
+__device__ __forceinline__ double sol_legendre_d(const double* cf, int n, double c) {
+  double u1 = 0.0, u2 = 0.0, d1 = 0.0, d2 = 0.0;
+  for (int j = n - 1; j >= 0; --j) {
+    const double g = (double)(2 * j + 1) / (double)(j + 1), al = g * c, be = (double)(j + 1) / (double)(j + 2);
+    const double dn = g * u1 + (al * d1 - be * d2);
+    const double un = cf[j] + (al * u1 - be * u2);
+    d2 = d1;
+    d1 = dn;
+    u2 = u1;
+    u1 = un;
+  }
+  return d1;
+}
+
+// Hz [NZ]: the node-variable columns of sum_r mult[r] d(f | p | g)_r / dz at v, from one eval_fj
+template <class M>
+__device__ __forceinline__ void sol_hgrad(const double* v, const double* mult, double* Hz) {
+  using St = S<M>;
+  constexpr int NZ = St::NZ, NJ = St::NJ, NFN = St::NFN;
+  double F[NFN > 0 ? NFN : 1], Jv[NJ > 0 ? NJ : 1];
+  M::eval_fj(v, F, Jv);
+  static_for<0, NZ>([&](auto b_) { Hz[decltype(b_)::value] = 0.0; });
+  static_for<0, NJ>([&](auto e_) {
+    constexpr int e = decltype(e_)::value;
+    if constexpr (M::jc(e) < NZ) Hz[M::jc(e)] += mult[M::jr(e)] * Jv[e];
+  });
+}
+
+template <class M>
+__device__ __forceinline__ void sol_multipliers(const PcSolMultiplierArgs& A) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NZ = St::NZ, NP = St::NP, NQ = St::NQ, NFN = St::NFN;
+  constexpr int NM = NP + NZ, NM1 = NM > 0 ? NM : 1;
+  extern __shared__ double smem[];
+  const int tid = threadIdx.x, TB = blockDim.x;
+  const PcPhaseView& V = A.v;
+  double* s_U = smem;
+  double* s_D = s_U + A.tab_total;
+  double* s_W = s_D + A.tab_total;
+  double* s_val = s_W + A.w_total;                      // [NP + NZ][TB] mu, then zeta
+  int* s_sec = reinterpret_cast<int*>(s_val + NM1 * TB);   // [TB] section of every lane
+  const double* sc = V.scal;
+  for (int i = tid; i < A.tab_total; i += TB) {
+    s_U[i] = A.tabU[i];
+    s_D[i] = A.tabD[i];
+  }
+  for (int i = tid; i < A.w_total; i += TB) s_W[i] = A.tabW[i];
+  const SolLane L = sol_lane_map(V, A.tile_k0[blockIdx.x], A.tile_k0[blockIdx.x + 1], A.lane0, 0, s_sec);
+  const bool has_z = A.z != nullptr;
+  double t0, tF;
+  sol_times<M>(V, t0, tF);
+  const double stretch = 0.5 * (tF - t0);
+  if (L.active) {
+    const int k = L.k, n = L.n, j = L.j, node = L.sk + j, N = V.N;
+    // the node weight, summed as pc_sol_costate sums it
+    int ka = k, pa = j, kb = k;
+    if (j == 0 && k > 0) { ka = k - 1; pa = L.sk - V.sec_s[k - 1]; }
+    if (j == n - 1 && k < V.K - 1) kb = k + 1;
+    double omega = 0.0;
+    for (int kk = ka; kk <= kb; ++kk) {
+      const int s0 = V.sec_s[kk], nn = V.sec_s[kk + 1] - s0 + 1, pos = kk == ka ? pa : 0;
+      omega += (A.sec_tau[kk + 1] - A.sec_tau[kk]) * s_W[A.offW[nn] + pos];
+    }
+    const bool weighted = !(node == N - 1 && omega == 0.0);
+    const bool owner = sol_owner(L, V.K);
+    const double den = stretch * omega, nan = __builtin_nan("");
+    double mult[NFN > 0 ? NFN : 1];
+    static_for<0, NY>([&](auto a_) { mult[decltype(a_)::value] = A.node_p[(int64_t) decltype(a_)::value * N + node]; });
+    static_for<0, NP>([&](auto i_) {
+      constexpr int i = decltype(i_)::value;
+      const double mu = weighted ? (sc[St::O_WP + i] * A.lam[A.c_path_off + (int64_t)i * N + node] / A.wJ) / den : nan;
+      mult[NY + i] = mu;
+      s_val[i * TB + tid] = weighted ? mu : 0.0;
+      if (owner) A.node_mu[(int64_t)i * N + node] = mu;
+    });
+    static_for<0, NQ>([&](auto m_) { mult[NY + NP + decltype(m_)::value] = A.int_scale * A.nu[decltype(m_)::value]; });
+    if (has_z) {
+      static_for<0, NZ>([&](auto b_) {
+        constexpr int b = decltype(b_)::value;
+        const double zs = A.z[V.x_off + (int64_t)b * N + node] / (A.wJ * sc[St::O_VZ + b]);
+        const bool end = b < NY && (node == 0 || node == N - 1);
+        const double zeta = end ? 0.0 : (weighted ? zs / den : nan);
+        s_val[(NP + b) * TB + tid] = weighted ? zeta : 0.0;
+        if (owner) {
+          A.node_zeta[(int64_t)b * N + node] = zeta;
+          if (end) A.end_z[2 * b + (node == 0 ? 0 : 1)] = zs;
+        }
+      });
+    }
+    double v[St::NV > 0 ? St::NV : 1], Hz[NZ > 0 ? NZ : 1];
+    sol_params<M>(V, v);
+    sol_node<M>(V, node, v);
+    sol_hgrad<M>(v, mult, Hz);
+    if (owner) static_for<0, NZ>([&](auto b_) {
+      A.node_Hz[(int64_t) decltype(b_)::value * N + node] = weighted ? Hz[decltype(b_)::value] : nan;
+    });
+  }
+  __syncthreads();
+  if (L.active) {
+    const int n = L.n;
+    const double* Tr = (L.k == V.K - 1 ? s_D : s_U) + A.offC[n] + L.j * n;
+    const int64_t slot = (int64_t)L.sk + L.k + L.j;
+    static_for<0, NP>([&](auto i_) {
+      constexpr int i = decltype(i_)::value;
+      A.coef_mu[(int64_t)i * A.NC + slot] = sol_row_dot(Tr, s_val + i * TB + L.l0, n);
+    });
+    if (has_z) static_for<0, NZ>([&](auto b_) {
+      constexpr int b = decltype(b_)::value;
+      A.coef_zeta[(int64_t)b * A.NC + slot] = sol_row_dot(Tr, s_val + (NP + b) * TB + L.l0, n);
+    });
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// pc_sol_sample_optimality_p<i>: one lane per query, located as in pc_sol_sample.  mu(t), zeta(t) and p(t) are the
+// sections' interpolants, dp/dt = 2 / (w_k stretch) d/dc of p's; H_y(t), H_u(t) from the tape at the interpolated
+// (y(t), u(t)) with p(t), mu(t) and rho nu.  Outputs variable-major [var][Q].
+// ---------------------------------------------------------------------------------------------
+template <class M>
+__device__ __forceinline__ void sol_sample_optimality(const PcSolOptimalitySampleArgs& B) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NU = St::NU, NZ = St::NZ, NP = St::NP, NQ = St::NQ, NFN = St::NFN;
+  const PcSolSampleArgs& A = B.s;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.Q) return;
+  const bool has_z = B.coef_zeta != nullptr;
+  SolSpot s;
+  if (!sol_locate<M>(A, i, s)) {
+    const double nan = __builtin_nan("");
+    static_for<0, NY>([&](auto a_) {
+      B.out_Hy[(int64_t) decltype(a_)::value * A.Q + i] = nan;
+      B.out_dp[(int64_t) decltype(a_)::value * A.Q + i] = nan;
+    });
+    static_for<0, NU>([&](auto b_) { B.out_Hu[(int64_t) decltype(b_)::value * A.Q + i] = nan; });
+    static_for<0, NP>([&](auto i_) { B.out_mu[(int64_t) decltype(i_)::value * A.Q + i] = nan; });
+    if (has_z) static_for<0, NZ>([&](auto b_) { B.out_zeta[(int64_t) decltype(b_)::value * A.Q + i] = nan; });
+    return;
+  }
+  double v[St::NV > 0 ? St::NV : 1], mult[NFN > 0 ? NFN : 1], Hz[NZ > 0 ? NZ : 1];
+  static_for<0, NY>([&](auto a_) {
+    double d;
+    v[decltype(a_)::value] = sol_state(A, s, decltype(a_)::value, d);
+  });
+  static_for<0, NU>([&](auto b_) {
+    constexpr int b = decltype(b_)::value;
+    v[NY + b] = sol_legendre(A.c.coef_u + (int64_t)b * A.c.NC + s.off, s.n, s.c);
+  });
+  sol_params<M>(A.v, v);
+  const double dcdt = 2.0 / (s.w * s.stretch);
+  static_for<0, NY>([&](auto a_) {
+    constexpr int a = decltype(a_)::value;
+    const double* cf = B.coef_p + (int64_t)a * A.c.NC + s.off;
+    mult[a] = sol_legendre(cf, s.n, s.c);
+    B.out_dp[(int64_t)a * A.Q + i] = dcdt * sol_legendre_d(cf, s.n, s.c);
+  });
+  static_for<0, NP>([&](auto i_) {
+    constexpr int ii = decltype(i_)::value;
+    const double mu = sol_legendre(B.coef_mu + (int64_t)ii * A.c.NC + s.off, s.n, s.c);
+    mult[NY + ii] = mu;
+    B.out_mu[(int64_t)ii * A.Q + i] = mu;
+  });
+  static_for<0, NQ>([&](auto m_) { mult[NY + NP + decltype(m_)::value] = B.int_scale * B.nu[decltype(m_)::value]; });
+  sol_hgrad<M>(v, mult, Hz);
+  static_for<0, NY>([&](auto a_) { B.out_Hy[(int64_t) decltype(a_)::value * A.Q + i] = Hz[decltype(a_)::value]; });
+  static_for<0, NU>([&](auto b_) { B.out_Hu[(int64_t) decltype(b_)::value * A.Q + i] = Hz[NY + decltype(b_)::value]; });
+  if (has_z) static_for<0, NZ>([&](auto b_) {
+    constexpr int b = decltype(b_)::value;
+    B.out_zeta[(int64_t)b * A.Q + i] = sol_legendre(B.coef_zeta + (int64_t)b * A.c.NC + s.off, s.n, s.c);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------
 // Propagation: dy/dc = stretch (w_k / 2) f(y, u(c), q, t0, tF, s) integrated by Dormand-Prince 5(4) across
 // node intervals, u(c) the section's control interpolant (sol_legendre on coef_u, what pc_sol_sample returns).
 //
@@ -711,7 +898,7 @@ __device__ __forceinline__ void mesh_error(const PcRefineArgs& A) {
 
 }  // namespace pc
 
-// the five entry points of phase I, instantiated by the generated source once per phase (pc_mesh_err_p<i> is emitted by
+// the seven entry points of phase I, instantiated by the generated source once per phase (pc_mesh_err_p<i> is emitted by
 // the generator itself)
 #define PC_SOL_ENTRY_POINTS(I)                                                                               \
   extern "C" __global__ void __launch_bounds__(256) pc_sol_fit_p##I(PcSolFitArgs a) {                        \
@@ -728,6 +915,12 @@ __device__ __forceinline__ void mesh_error(const PcRefineArgs& A) {
   }                                                                                                          \
   extern "C" __global__ void __launch_bounds__(PC_SOL_PROP_TB) pc_sol_propagate_p##I(PcSolPropagateArgs a) { \
     pc::sol_propagate<gen::Phase##I>(a);                                                                     \
+  }                                                                                                          \
+  extern "C" __global__ void __launch_bounds__(256) pc_sol_multipliers_p##I(PcSolMultiplierArgs a) {         \
+    pc::sol_multipliers<gen::Phase##I>(a);                                                                   \
+  }                                                                                                          \
+  extern "C" __global__ void __launch_bounds__(256) pc_sol_sample_optimality_p##I(PcSolOptimalitySampleArgs a) { \
+    pc::sol_sample_optimality<gen::Phase##I>(a);                                                             \
   }
 
 #endif  // PC_SOLUTION_HPP

@@ -13,20 +13,34 @@
 //
 // Propagation (pc_solution_propagate): the index arithmetic is pc_propagate_plan.hpp.  The segment list, the first
 // sections and atol are staged in buffers the solution keeps, so a device call may return before the kernel has run.
+//
+// Path and bound multipliers (pc_solution_set_bound_multipliers): the index arithmetic is pc_optimality_plan.hpp.  The
+// solution keeps its own device copy of the constraint multipliers, the tables and the scaling they were set under, so
+// this call may come any time after pc_solution_set_multipliers.
 #include "pc_costate_plan.hpp"
+#include "pc_optimality_plan.hpp"
 #include "pc_propagate_plan.hpp"
 
 struct pc_solution {
   pc_handle* h = nullptr;
   DevBuf<double> d_x;
   DevBuf<double> d_U;       // the C_u tables (the costate kernel forms its coefficients with them)
-  DevBuf<double> d_lam;     // a host multiplier vector's device copy
-  bool has_costate = false;
+  DevBuf<double> d_D;       // the ydot tables (the multiplier kernel: the phase's last section)
+  DevBuf<double> d_lam;     // the multiplier vector's device copy
+  DevBuf<double> d_W, d_z;  // the node-weight rows of the A tables; the bound multipliers' device copy
+  std::vector<int32_t> orders;   // as of pc_solution_set_multipliers
+  std::vector<double> tabA;
+  double wJ = 0.0;          // the objective scaling the multipliers were set under
+  double int_scale = 1.0;   // pcs::integral_weight_scale of the handle's tables
+  bool has_costate = false, has_optimality = false, has_z = false;
   struct Phase {
     pcs::FitPlan plan;
     DevBuf<int32_t> tile_k0, lane0;
     DevBuf<double> sec_tau, node_tau, node_t, node_y, node_u, node_f, coef_dy, coef_u;
     DevBuf<double> node_p, node_H, coef_p, nu;   // costates: allocated by pc_solution_set_multipliers
+    DevBuf<double> node_mu, node_zeta, end_z, node_Hz, coef_mu, coef_zeta;   // by pc_solution_set_bound_multipliers
+    hipFunction_t fn_sample_optimality = nullptr;
+    PcPhaseView view_w;     // view with the constraint scaling the multipliers were set under
     DevBuf<int32_t> prop_seg, prop_sec;          // propagation: the staged segment list and first sections,
     DevBuf<double> prop_atol;                    // and atol
     hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr, fn_propagate = nullptr;
@@ -44,7 +58,7 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
   pc_handle* h = s->h;
   auto& Q = h->Q;
   if (!tabD || !tabU || !tau) throw std::runtime_error("solution: null table");
-  DevBuf<double> d_D;
+  DevBuf<double>& d_D = s->d_D;
   int32_t offC[PC_MAX_ORDER + 1];
   const int32_t tab_total = pcs::table_offsets(n_orders, orders, offC);
   d_D.upload(std::vector<double>(tabD, tabD + tab_total));
@@ -96,7 +110,7 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     a.tab_total = F.tab_total;
     std::memcpy(a.offC, F.offC, sizeof(a.offC));
     launch_block(fn_fit, F.n_tiles(), F.TB, F.lds_bytes, h->stream, a);
-    HIP_OK(hipStreamSynchronize(h->stream));   // the tables above are released on return
+    HIP_OK(hipStreamSynchronize(h->stream));
     s->ph.push_back(std::move(S));
   }
 }
@@ -171,9 +185,14 @@ void solution_costate(pc_solution* s, const double* d_lam, int n_orders, const i
     std::memcpy(a.offC, F.offC, sizeof(a.offC));
     std::memcpy(a.offA, C.offA, sizeof(a.offA));
     launch_block(fn, F.n_tiles(), F.TB, C.lds_bytes, h->stream, a);
+    S.view_w = a.v;
   }
-  HIP_OK(hipStreamSynchronize(h->stream));   // d_A is released on return; a caller's device vector is free again
+  HIP_OK(hipStreamSynchronize(h->stream));   // d_A is released on return
+  s->orders.assign(orders, orders + n_orders);
+  s->tabA.assign(tabA, tabA + a_total);
+  s->wJ = h->scal.wJ;
   s->has_costate = true;
+  s->has_optimality = s->has_z = false;       // (they belong to the multipliers that were just replaced)
 }
 
 int solution_set_multipliers(pc_solution* s, const double* lam, int64_t n_lam, bool on_device, int n_orders, const int32_t* orders,
@@ -183,13 +202,11 @@ int solution_set_multipliers(pc_solution* s, const double* lam, int64_t n_lam, b
     require_device(s->h);
     pcs::check_multiplier_args(lam, n_lam, s->h->Q.num_c, tabA, s->h->scal.wJ);
     HIP_OK(hipSetDevice(s->h->device));
-    const double* d_lam = lam;
-    if (!on_device) {
-      if (s->d_lam.n != (size_t)n_lam) s->d_lam.alloc((size_t)n_lam);
-      HIP_OK(hipMemcpyAsync(s->d_lam.p, lam, (size_t)n_lam * sizeof(double), hipMemcpyHostToDevice, s->h->stream));
-      d_lam = s->d_lam.p;
-    }
-    solution_costate(s, d_lam, n_orders, orders, tabA);
+    // the solution's own copy: the path multipliers are read from it later (pc_solution_set_bound_multipliers)
+    if (s->d_lam.n != (size_t)n_lam) s->d_lam.alloc((size_t)n_lam);
+    HIP_OK(hipMemcpyAsync(s->d_lam.p, lam, (size_t)n_lam * sizeof(double),
+                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->h->stream));
+    solution_costate(s, s->d_lam.p, n_orders, orders, tabA);
   });
 }
 
@@ -208,6 +225,111 @@ void solution_launch_sample_costate(pc_solution* s, int phase, const double* d_t
   a.out_p = d_p;
   a.out_H = d_H;
   launch_block(S.fn_sample_costate, (unsigned)pcs::sample_blocks(n_t, 256), 256, 0, s->h->stream, a);
+}
+
+// mu, zeta and the node gradients of every phase (pc_sol_multipliers_p<i>) from the solution's multipliers and d_z (or
+// null), then the arguments of the sampling call
+void solution_optimality(pc_solution* s, const double* d_z) {
+  pc_handle* h = s->h;
+  auto& Q = h->Q;
+  const int n_orders = (int)s->orders.size();
+  int32_t offA[PC_MAX_ORDER + 1], offW[PC_MAX_ORDER + 1];
+  (void)pcs::a_table_offsets(n_orders, s->orders.data(), offA);
+  const int32_t w_total = pcs::w_table_offsets(n_orders, s->orders.data(), offW);
+  s->d_W.upload(pcs::pack_weight_rows(n_orders, s->orders.data(), s->tabA.data(), offA, offW, w_total));
+  s->int_scale = pcs::integral_weight_scale(n_orders, s->orders.data(), s->tabA.data(), offA, h->qw.data(), h->qw_off);
+  for (size_t ip = 0; ip < Q.ph.size(); ++ip) {
+    auto& P = Q.ph[ip];
+    auto& S = *s->ph[ip];
+    const pcs::FitPlan& F = S.plan;
+    const pcs::OptimalityPlan O = pcs::build_optimality_plan(F, n_orders, s->orders.data(), P.n_y, P.n_u, P.n_p, P.c_path_off,
+                                                             P.c_int_off, Q.num_c, P.x_off, Q.num_x, h->lds_limit);
+    const size_t nz = (size_t)std::max(1, P.n_y + P.n_u), np = (size_t)std::max(1, P.n_p);
+    if (!S.node_mu.p) {
+      S.node_mu.alloc(np * F.N);
+      S.coef_mu.alloc(np * F.NC);
+      S.node_Hz.alloc(nz * F.N);
+    }
+    if (d_z && !S.node_zeta.p) {
+      S.node_zeta.alloc(nz * F.N);
+      S.coef_zeta.alloc(nz * F.NC);
+      S.end_z.alloc(2 * (size_t)std::max(1, P.n_y));
+    }
+    hipFunction_t fn = nullptr;
+    HIP_OK(find_fn(h, &fn, ("pc_sol_multipliers_p" + std::to_string(ip)).c_str()));
+    HIP_OK(find_fn(h, &S.fn_sample_optimality, ("pc_sol_sample_optimality_p" + std::to_string(ip)).c_str()));
+    PcSolMultiplierArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.v = S.view_w;
+    a.lam = s->d_lam.p;
+    a.z = d_z;
+    a.tile_k0 = S.tile_k0.p;
+    a.lane0 = S.lane0.p;
+    a.sec_tau = S.sec_tau.p;
+    a.tabW = s->d_W.p;
+    a.tabU = s->d_U.p;
+    a.tabD = s->d_D.p;
+    a.node_p = S.node_p.p;
+    a.nu = S.nu.p;
+    a.node_mu = S.node_mu.p;
+    a.node_zeta = S.node_zeta.p;
+    a.end_z = S.end_z.p;
+    a.node_Hz = S.node_Hz.p;
+    a.coef_mu = S.coef_mu.p;
+    a.coef_zeta = S.coef_zeta.p;
+    a.c_path_off = P.c_path_off;
+    a.wJ = s->wJ;
+    a.int_scale = s->int_scale;
+    a.NC = F.NC;
+    a.tab_total = F.tab_total;
+    a.w_total = w_total;
+    std::memcpy(a.offC, F.offC, sizeof(a.offC));
+    std::memcpy(a.offW, O.offW, sizeof(a.offW));
+    launch_block(fn, F.n_tiles(), F.TB, O.lds_bytes, h->stream, a);
+  }
+  HIP_OK(hipStreamSynchronize(h->stream));   // a caller's device vector is free again
+  s->has_optimality = true;
+  s->has_z = d_z != nullptr;
+}
+
+int solution_set_bound_multipliers(pc_solution* s, const double* z, int64_t n_z, bool on_device) {
+  return guarded(g_err, [&] {
+    if (!s) throw std::runtime_error("null solution");
+    require_device(s->h);
+    pcs::check_bound_multiplier_args(s->has_costate, z, n_z, s->h->Q.num_x);
+    HIP_OK(hipSetDevice(s->h->device));
+    const double* d_z = z;
+    if (z && !on_device) {
+      if (s->d_z.n != (size_t)n_z) s->d_z.alloc((size_t)n_z);
+      HIP_OK(hipMemcpyAsync(s->d_z.p, z, (size_t)n_z * sizeof(double), hipMemcpyHostToDevice, s->h->stream));
+      d_z = s->d_z.p;
+    }
+    solution_optimality(s, d_z);
+  });
+}
+
+void solution_launch_sample_optimality(pc_solution* s, int phase, const double* d_t, int64_t n_t, int flags, double* d_Hy,
+                                       double* d_Hu, double* d_dp, double* d_mu, double* d_zeta) {
+  auto& S = *s->ph[phase];
+  if (n_t == 0) return;
+  PcSolOptimalitySampleArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.s.v = S.view;
+  a.s.c = S.curves;
+  a.s.t = d_t;
+  a.s.Q = n_t;
+  a.s.flags = flags;
+  a.coef_p = S.coef_p.p;
+  a.nu = S.nu.p;
+  a.coef_mu = S.coef_mu.p;
+  a.coef_zeta = s->has_z ? S.coef_zeta.p : nullptr;
+  a.int_scale = s->int_scale;
+  a.out_Hy = d_Hy;
+  a.out_Hu = d_Hu;
+  a.out_dp = d_dp;
+  a.out_mu = d_mu;
+  a.out_zeta = d_zeta;
+  launch_block(S.fn_sample_optimality, (unsigned)pcs::sample_blocks(n_t, 256), 256, 0, s->h->stream, a);
 }
 
 int solution_create(pc_handle* h, const double* x, bool x_on_device, int n_orders, const int32_t* orders, const double* tabD,
@@ -273,6 +395,12 @@ pc_solution::Phase& solution_costate_phase(pc_solution* s, int phase) {
 
 void solution_down(double* dst, const DevBuf<double>& src, size_t count) {
   if (dst && count) HIP_OK(hipMemcpy(dst, src.p, count * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+pc_solution::Phase& solution_optimality_phase(pc_solution* s, int phase) {
+  auto& S = solution_phase(s, phase);
+  if (!s->has_optimality) throw std::runtime_error("optimality: pc_solution_set_bound_multipliers has not run");
+  return S;
 }
 
 }  // namespace
@@ -412,6 +540,87 @@ int pc_solution_sample_costate_device(pc_solution* sol, int phase, const double*
     auto& S = solution_costate_phase(sol, phase);
     if (n_t > 0 && (!d_H || (S.NY > 0 && !d_p))) throw std::runtime_error("solution: null output");
     solution_launch_sample_costate(sol, phase, d_t, n_t, flags, d_p, d_H);
+  });
+}
+
+int pc_solution_set_bound_multipliers(pc_solution* sol, const double* z, int64_t n_z) {
+  return solution_set_bound_multipliers(sol, z, n_z, false);
+}
+
+int pc_solution_set_bound_multipliers_device(pc_solution* sol, const double* d_z, int64_t n_z) {
+  return solution_set_bound_multipliers(sol, d_z, n_z, true);
+}
+
+int pc_solution_multiplier_nodes(pc_solution* sol, int phase, double* mu, double* zeta, double* end_z, double* H_y, double* H_u) {
+  return guarded(g_err, [&] {
+    auto& S = solution_optimality_phase(sol, phase);
+    const size_t N = (size_t)S.plan.N, NP = (size_t)sol->h->Q.ph[(size_t)phase].n_p;
+    if ((zeta || end_z) && !sol->has_z) throw std::runtime_error("optimality: no bound multipliers were given");
+    solution_down(mu, S.node_mu, N * NP);
+    solution_down(zeta, S.node_zeta, N * (size_t)(S.NY + S.NU));
+    solution_down(end_z, S.end_z, 2 * (size_t)S.NY);
+    solution_down(H_y, S.node_Hz, N * S.NY);
+    if (H_u && S.NU) HIP_OK(hipMemcpy(H_u, S.node_Hz.p + N * S.NY, N * S.NU * sizeof(double), hipMemcpyDeviceToHost));
+  });
+}
+
+int pc_solution_defect_multipliers(pc_solution* sol, int phase, double* Lam) {
+  return guarded(g_err, [&] {
+    auto& S = solution_costate_phase(sol, phase);
+    const auto& P = sol->h->Q.ph[(size_t)phase];
+    const size_t rows = (size_t)S.plan.N - 1, o_wd = sol->h->scal.phase[(size_t)phase].size() - (size_t)(P.n_y + P.n_p + P.n_q);
+    if (!Lam || !S.NY) return;
+    HIP_OK(hipMemcpy(Lam, sol->d_lam.p + P.c_off, rows * S.NY * sizeof(double), hipMemcpyDeviceToHost));
+    for (int a = 0; a < S.NY; ++a)   // (the operation order of pc_sol_costate)
+      for (size_t r = 0; r < rows; ++r) Lam[(size_t)a * rows + r] = S.view_w.scal[o_wd + (size_t)a] * Lam[(size_t)a * rows + r] / sol->wJ;
+  });
+}
+
+int pc_solution_multiplier_coefficients(pc_solution* sol, int phase, double* mu_coef, double* zeta_coef) {
+  return guarded(g_err, [&] {
+    auto& S = solution_optimality_phase(sol, phase);
+    if (zeta_coef && !sol->has_z) throw std::runtime_error("optimality: no bound multipliers were given");
+    solution_down(mu_coef, S.coef_mu, (size_t)S.plan.NC * (size_t)sol->h->Q.ph[(size_t)phase].n_p);
+    solution_down(zeta_coef, S.coef_zeta, (size_t)S.plan.NC * (size_t)(S.NY + S.NU));
+  });
+}
+
+int pc_solution_sample_optimality(pc_solution* sol, int phase, const double* t, int64_t n_t, int flags, double* H_y, double* H_u,
+                                  double* dp, double* mu, double* zeta) {
+  return guarded(g_err, [&] {
+    if (!sol) throw std::runtime_error("null solution");
+    pcs::check_sample_args((int)sol->ph.size(), phase, t, n_t, flags);
+    auto& S = solution_optimality_phase(sol, phase);
+    if (n_t == 0) return;
+    const size_t Qn = (size_t)n_t, NP = (size_t)sol->h->Q.ph[(size_t)phase].n_p, NZ = (size_t)(S.NY + S.NU);
+    DevBuf<double> d_t, d_Hy, d_Hu, d_dp, d_mu, d_zeta;
+    d_t.upload(std::vector<double>(t, t + Qn));
+    d_Hy.alloc(Qn * (size_t)std::max(1, S.NY));
+    d_Hu.alloc(Qn * (size_t)std::max(1, S.NU));
+    d_dp.alloc(Qn * (size_t)std::max(1, S.NY));
+    d_mu.alloc(Qn * std::max<size_t>(1, NP));
+    d_zeta.alloc(Qn * std::max<size_t>(1, NZ));
+    solution_launch_sample_optimality(sol, phase, d_t.p, n_t, flags, d_Hy.p, d_Hu.p, d_dp.p, d_mu.p, d_zeta.p);
+    HIP_OK(hipStreamSynchronize(sol->h->stream));
+    solution_down(H_y, d_Hy, Qn * S.NY);
+    solution_down(H_u, d_Hu, Qn * S.NU);
+    solution_down(dp, d_dp, Qn * S.NY);
+    solution_down(mu, d_mu, Qn * NP);
+    if (sol->has_z) solution_down(zeta, d_zeta, Qn * NZ);
+  });
+}
+
+int pc_solution_sample_optimality_device(pc_solution* sol, int phase, const double* d_t, int64_t n_t, int flags, double* d_H_y,
+                                         double* d_H_u, double* d_dp, double* d_mu, double* d_zeta) {
+  return guarded(g_err, [&] {
+    if (!sol) throw std::runtime_error("null solution");
+    pcs::check_sample_args((int)sol->ph.size(), phase, d_t, n_t, flags);
+    auto& S = solution_optimality_phase(sol, phase);
+    const int NP = sol->h->Q.ph[(size_t)phase].n_p;
+    if (n_t > 0 && ((S.NY > 0 && (!d_H_y || !d_dp)) || (S.NU > 0 && !d_H_u) || (NP > 0 && !d_mu) ||
+                    (sol->has_z && S.NY + S.NU > 0 && !d_zeta)))
+      throw std::runtime_error("optimality: null output");
+    solution_launch_sample_optimality(sol, phase, d_t, n_t, flags, d_H_y, d_H_u, d_dp, d_mu, d_zeta);
   });
 }
 

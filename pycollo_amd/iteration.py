@@ -226,11 +226,19 @@ class MeshIteration:
         controls are those of :meth:`solution`; they are unscaled with the scaling the NLP functions were generated
         with (the engine's), which is this iteration's unless ``update_scaling`` averaged it afterwards.  When an
         interior-point solve has run, its multipliers (``result.lam``) are passed on and the solution carries
-        ``costate`` / ``hamiltonian`` / ``integrand_multiplier``."""
+        ``costate`` / ``hamiltonian`` / ``integrand_multiplier``; its bound multipliers (``result.zl`` / ``result.zu``) are
+        passed on too where it reports them."""
         from .solution import Solution
         # after an interior-point solve the multipliers of every row come along: costates and the Hamiltonian
-        lam = getattr(getattr(self, "result", None), "lam", None)
-        return Solution(self.engine, self.x_tilde, objective=getattr(self, "objective", None), multipliers=lam)
+        res = getattr(self, "result", None)
+        lam = getattr(res, "lam", None)
+        # ... and the bound multipliers where the solver reports them: path and bound multiplier functions, H_y, H_u
+        zl, zu = getattr(res, "zl", None), getattr(res, "zu", None)
+        bounds = None
+        if lam is not None and zl is not None and zu is not None:
+            bounds = (np.ascontiguousarray(zl, dtype=np.float64), np.ascontiguousarray(zu, dtype=np.float64))
+        return Solution(self.engine, self.x_tilde, objective=getattr(self, "objective", None), multipliers=lam,
+                        bound_multipliers=bounds)
 
     def solve_with_scipy(self, maxiter: int = 500, tol: float = 1e-9, verbose: int = 0):
         """Solve the scaled NLP with scipy's trust-region interior point method (stand-in for IPOPT)."""

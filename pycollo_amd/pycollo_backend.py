@@ -367,14 +367,16 @@ class Mi355x:
             raise MemoryError("G_iter_scale_callable densifies G; use Mi355x.constraint_row_norms(x) at this size")
         return self._with_scaling(W, self.engine.w_J, lambda: self.engine.evaluate_G(x).toarray())
 
-    def solution(self, x, objective=None, lam_g=None):
+    def solution(self, x, objective=None, lam_g=None, lam_x=None):
         """The scaled NLP point ``x`` of the current mesh iteration as a :class:`pycollo_amd.solution.Solution`: what
         ``CasadiSolution`` extracts and interpolates (solution/casadi_solution.py:15-86, solution_abc.py:60-142), the
         state derivatives from the device instead of :meth:`_dy`'s host evaluation.  ``lam_g``: the solver's constraint
-        multipliers at ``x`` (``nlp_result["lam_g"]``); with them the solution carries costates and the Hamiltonian."""
+        multipliers at ``x`` (``nlp_result["lam_g"]``); with them the solution carries costates and the Hamiltonian.
+        ``lam_x``: the solver's signed bound multipliers (``nlp_result["lam_x"]``, needs ``lam_g``); with them the bound
+        multiplier functions enter ``control_stationarity`` and the costate residuals."""
         from .solution import Solution
-        return Solution(self.engine, x, objective=objective,
-                        multipliers=None if lam_g is None else np.ascontiguousarray(lam_g, dtype=np.float64).reshape(-1))
+        flat = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1)   # noqa: E731
+        return Solution(self.engine, x, objective=objective, multipliers=flat(lam_g), bound_multipliers=flat(lam_x))
 
     def _dy(self, x):
         """``dy_iter_callable(x)`` (backend.py:1551-1556, 1666-1668): the state derivatives f(y, u, q, t, s) at every

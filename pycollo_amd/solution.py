@@ -45,6 +45,26 @@ W the per-OCP-row constraint scaling the handle holds.  Then:
   Legendre coefficients formed with the ``C_u`` table like u; H(t) is formed from the interpolated p(t) and the model
   at the interpolated (y(t), u(t)), the route by which ``sample(..., residual=True)`` forms f.
 
+Path and bound multipliers, the gradients of the augmented Hamiltonian (``bound_multipliers=``; no reference counterpart;
+DESIGN 8f).  With stretch, omega_j, w, W and Lam as above, V the variable scaling and z~ = zu - zl the signed bound
+multipliers of the scaled NLP's ``num_x`` variables:
+
+* mu_i(j) = W_p,i lam~[c_path_off + i N + j] / (w stretch omega_j): the multiplier function of path row i.
+* zeta_v(j) = z~[x_off + v N + j] / (w V_v stretch omega_j), v over the n_y states and then the n_u controls.  A state's
+  bound at nodes 0 and N - 1 is the endpoint bound: zeta_y is 0 there and z~ / (w V_a) is ``endpoint_bound_multiplier``
+  [n_y][2].
+* H_z(j) = sum_a p_a df_a/dz + sum_i mu_i dp_i/dz + sum_m rho nu_m dg_m/dz for a node variable z, from the generated
+  first partials in table order.  rho is the weight the NLP's integral rows give a node over omega_j: 1 under Lobatto, 2
+  under Radau, whose rule weights sum to 2 where the last row of A sums to 1 (``hamiltonian`` keeps nu_m alone).  At the
+  Radau phase-final node mu, zeta_u and H_z are NaN.
+* ``control_stationarity`` = H_u + zeta_u and ``costate_defect`` = D_a / (stretch omega) + H_y + zeta_y with
+  D_a(j) = sum_{r < n_k - 1} Lam_a[s_k + r] if j opens section k, minus Lam_a[j - 1] if j >= 1: the dual residual of the
+  scaled NLP over w V stretch omega, column by column.
+* Between the nodes mu and zeta are held like u and p (the phase's last section: formed with the ydot table, which
+  under Radau leaves the final node out); dp/dt = 2 / (h_k stretch) d/dc of the costate's Legendre series; H_y(t), H_u(t)
+  are formed at the interpolated (y(t), u(t)) with p(t), mu(t) and rho nu.  ``costate_residual`` = dp + H_y + zeta_y.
+* All of it is formed on first use (``pc_sol_multipliers_p<i>``, one launch per phase).
+
 Propagation (:meth:`Solution.propagate`; no reference counterpart): the dynamics integrated forward under the
 solution's control interpolant by the Dormand-Prince 5(4) pair, restarted from the NLP's own state at chosen nodes
 (``pc_sol_propagate_p<i>``, one lane per restart).  ``defect = y_arrive - state`` is what the collocation residual
@@ -182,6 +202,69 @@ def _is_torch(t) -> bool:
     return hasattr(t, "data_ptr") and hasattr(t, "device")
 
 
+def signed_bound_multipliers(bound_multipliers, num_x: int, has_multipliers: bool):
+    """``Solution``'s ``bound_multipliers`` as one signed vector zu - zl of ``num_x`` float64 entries (a NumPy array, or
+    a CUDA tensor when one was given), or ``None``.  Accepted: a pair ``(zl, zu)`` or one signed vector, host arrays or
+    device tensors, contiguous float64 of ``num_x`` entries.  ``ValueError`` otherwise, and when bound multipliers
+    come without constraint multipliers.  Touches no device."""
+    if bound_multipliers is None:
+        return None
+    if not has_multipliers:
+        raise ValueError("bound_multipliers need multipliers: the costates they are read with come from them")
+
+    def one(v):
+        if _is_torch(v):
+            import torch
+            if v.dtype != torch.float64 or v.dim() != 1 or v.numel() != num_x or not v.is_contiguous():
+                raise ValueError(f"bound_multipliers must be contiguous float64 vectors of {num_x} entries")
+            return v
+        v = np.asarray(v)
+        if v.dtype != np.float64 or v.shape != (num_x,) or not v.flags.c_contiguous:
+            raise ValueError(f"bound_multipliers must be contiguous float64 vectors of {num_x} entries")
+        return v
+
+    if isinstance(bound_multipliers, (tuple, list)):
+        if len(bound_multipliers) != 2:
+            raise ValueError("bound_multipliers must be a pair (zl, zu) or one signed vector")
+        zl, zu = (one(v) for v in bound_multipliers)
+        if _is_torch(zl) != _is_torch(zu):
+            raise ValueError("bound_multipliers: zl and zu must both be host arrays or both device tensors")
+        return zu - zl
+    return one(bound_multipliers)
+
+
+@dataclasses.dataclass
+class OptimalitySample:
+    """What :meth:`Solution.sample_optimality` returns (NumPy arrays, or torch tensors where the queries live):
+    ``H_y`` [n_y][Q], ``H_u`` [n_u][Q], ``dp`` = dp/dt [n_y][Q], ``mu`` [n_p][Q], ``zeta`` [n_y + n_u][Q] (``None``
+    without bound multipliers), ``costate_residual`` = dp + H_y (+ zeta_y), ``control_stationarity`` = H_u (+ zeta_u)."""
+    H_y: object
+    H_u: object
+    dp: object
+    mu: object
+    zeta: object
+    costate_residual: object
+    control_stationarity: object
+
+
+@dataclasses.dataclass
+class OptimalityReport:
+    """What :meth:`Solution.optimality_report` returns.  Per section [K]: ``control_stationarity`` / ``costate_residual``
+    (the maxima of their absolute values over the section's samples, 0 where the phase has no control / state) and
+    ``control_stationarity_time`` / ``costate_residual_time`` (where).  ``max_*``: the phase maxima; ``interior_max_*``:
+    with the first and last section left out (NaN when the phase has no other).  ``has_bound_multipliers``: whether zeta
+    is part of the two residuals."""
+    control_stationarity: np.ndarray
+    control_stationarity_time: np.ndarray
+    costate_residual: np.ndarray
+    costate_residual_time: np.ndarray
+    max_control_stationarity: float
+    max_costate_residual: float
+    interior_max_control_stationarity: float
+    interior_max_costate_residual: float
+    has_bound_multipliers: bool
+
+
 END_SLACK = 8 * np.finfo(float).eps     # csrc/pc_args.h PC_SOL_END_SLACK
 
 
@@ -218,15 +301,22 @@ def normalise_query(t, tau):
 
 
 class Solution:
-    """``Solution(engine, x_tilde, objective=None, multipliers=None)``: the NLP point ``x_tilde`` (scaled; a NumPy array
+    """``Solution(engine, x_tilde, objective=None, multipliers=None, bound_multipliers=None)``: the NLP point ``x_tilde`` (scaled; a NumPy array
     or a torch device tensor, e.g. the resident solver's iterate) of ``engine`` as node values and dense output.
     ``multipliers``: the scaled multipliers of the ``engine.num_c`` constraint rows at that point (NumPy array or torch
     device tensor, contiguous float64), belonging to the scaling the engine holds now; with them ``costate``
     ([n_y][N] per phase), ``hamiltonian`` ([N] per phase) and ``integrand_multiplier`` ([n_q] per phase) are filled and
-    :meth:`sample_costate` works; without them the three are ``None``.  Holds device memory: ``close()`` it (or let it
+    :meth:`sample_costate` works; without them the three are ``None``.  ``bound_multipliers``: the multipliers of the ``engine.num_x`` variable bounds,
+    a pair ``(zl, zu)`` or one signed vector ``zu - zl`` (needs ``multipliers``); the path and bound multipliers, the
+    gradients of the augmented Hamiltonian and the two Pontryagin residuals (``path_multiplier``, ``bound_multiplier``,
+    ``endpoint_bound_multiplier``, ``hamiltonian_gradient``, ``control_stationarity``, ``costate_defect``,
+    :meth:`sample_optimality`, :meth:`optimality_report`) are formed on first use.  Holds device memory: ``close()`` it (or let it
     go) before the engine is closed."""
 
-    def __init__(self, engine, x_tilde, objective=None, multipliers=None):
+    def __init__(self, engine, x_tilde, objective=None, multipliers=None, bound_multipliers=None):
+        self._h = None
+        self._optimality = None
+        self._z = signed_bound_multipliers(bound_multipliers, engine.num_x, multipliers is not None)
         self.engine = engine
         self._lib = engine._lib
         self._h = C.c_void_p()
@@ -326,6 +416,13 @@ class Solution:
         prop = [vp, C.c_int, C.c_int64, vp, C.c_int64, C.c_double, vp, C.c_int64, vp, vp, vp, vp]
         lib.pc_solution_propagate.argtypes = prop
         lib.pc_solution_propagate_device.argtypes = prop
+        lib.pc_solution_set_bound_multipliers.argtypes = [vp, vp, C.c_int64]
+        lib.pc_solution_set_bound_multipliers_device.argtypes = [vp, vp, C.c_int64]
+        lib.pc_solution_multiplier_nodes.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+        lib.pc_solution_multiplier_coefficients.argtypes = [vp, C.c_int, vp, vp]
+        lib.pc_solution_defect_multipliers.argtypes = [vp, C.c_int, vp]
+        lib.pc_solution_sample_optimality.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
+        lib.pc_solution_sample_optimality_device.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
         lib._pc_solution_declared = True
 
     def _set_multipliers(self, lam, orders):
@@ -520,6 +617,179 @@ class Solution:
         p, H = self._sample_into(self._lib.pc_solution_sample_costate, self._lib.pc_solution_sample_costate_device, phase, q,
                                  flags, [(pl.n_y, Q), (Q,)])
         return p, H
+
+    # ---- path and bound multipliers, the gradients of the augmented Hamiltonian --------------------
+    def _form_optimality(self):
+        """``pc_solution_set_bound_multipliers`` (one launch per phase) and the node values; once."""
+        if self._optimality is not None:
+            return self._optimality
+        if self.costate is None:
+            raise ValueError("the solution was made without multipliers: it has no path or bound multipliers")
+        if not self._h:
+            raise ValueError("the solution is closed")
+        z, eng = self._z, self.engine
+        if z is None:
+            ok = self._lib.pc_solution_set_bound_multipliers(self._h, None, 0)
+        elif _is_torch(z):
+            import torch
+            if not z.is_cuda:
+                raise ValueError("a tensor of bound multipliers must be on the GPU")
+            torch.cuda.current_stream(z.device).synchronize()
+            ok = self._lib.pc_solution_set_bound_multipliers_device(self._h, z.data_ptr(), z.numel())
+        else:
+            ok = self._lib.pc_solution_set_bound_multipliers(self._h, z.ctypes.data, z.shape[0])
+        self._check(ok)
+        ptr = lambda a: a.ctypes.data if (a is not None and a.size) else None   # noqa: E731
+        mu, zeta, end_z, H_y, H_u, defect = [], [], [], [], [], []
+        for ip, (pm, pl, mesh) in enumerate(zip(eng.model.phases, eng.layout.phases, eng.meshes)):
+            N, n_y, n_u = pl.N, pm.n_y, pm.n_u
+            m, hy, hu = np.empty((pm.n_p, N)), np.empty((n_y, N)), np.empty((n_u, N))
+            zt = np.empty((n_y + n_u, N)) if z is not None else None
+            ez = np.empty((n_y, 2)) if z is not None else None
+            self._check(self._lib.pc_solution_multiplier_nodes(self._h, ip, ptr(m), ptr(zt), ptr(ez), ptr(hy), ptr(hu)))
+            # the discrete defect term D_a(j) over stretch omega_j, at the interior weighted nodes
+            Lam = np.empty((n_y, N - 1))     # W lam~ / w from the solution's own device copy, as the multipliers were set
+            self._check(self._lib.pc_solution_defect_multipliers(self._h, ip, ptr(Lam)))
+            D = np.zeros((n_y, N))
+            D[:, 1:] -= Lam
+            for k in range(mesh.K):
+                s, n = int(mesh.s[k]), int(mesh.n[k])
+                D[:, s] += np.sum(Lam[:, s:s + n - 1], axis=1)
+            omega = self.quadrature_weights(ip)
+            stretch = 0.5 * (self.final_time[ip] - self.initial_time[ip])
+            cd = np.full((n_y, N), np.nan)
+            use = omega != 0
+            use[0] = use[-1] = False
+            cd[:, use] = D[:, use] / (stretch * omega[use]) + hy[:, use] + (zt[:n_y, use] if zt is not None else 0.0)
+            mu.append(m)
+            zeta.append(zt)
+            end_z.append(ez)
+            H_y.append(hy)
+            H_u.append(hu)
+            defect.append(cd)
+        self._optimality = dict(mu=tuple(mu), zeta=None if z is None else tuple(zeta),
+                                end_z=None if z is None else tuple(end_z), H_y=tuple(H_y), H_u=tuple(H_u),
+                                defect=tuple(defect))
+        return self._optimality
+
+    def _optimality_or_none(self, key):
+        if self.costate is None:
+            return None
+        return self._form_optimality()[key]
+
+    @property
+    def path_multiplier(self):
+        """mu [n_p][N] per phase; ``None`` without multipliers.  Formed on first use, like the five below."""
+        return self._optimality_or_none("mu")
+
+    @property
+    def bound_multiplier(self):
+        """zeta [n_y + n_u][N] per phase (states first); ``None`` without bound multipliers."""
+        return self._optimality_or_none("zeta")
+
+    @property
+    def endpoint_bound_multiplier(self):
+        """z~ / (w V_a) [n_y][2] per phase at nodes 0 and N - 1: the endpoint bounds' multipliers (transversality);
+        ``None`` without bound multipliers."""
+        return self._optimality_or_none("end_z")
+
+    @property
+    def hamiltonian_gradient(self):
+        """``(H_y, H_u)``: per phase [n_y][N] and [n_u][N], at the nodes' NLP values; ``None`` without multipliers."""
+        if self.costate is None:
+            return None
+        o = self._form_optimality()
+        return o["H_y"], o["H_u"]
+
+    @property
+    def control_stationarity(self):
+        """H_u + zeta_u [n_u][N] per phase (H_u alone without bound multipliers); ``None`` without multipliers."""
+        if self.costate is None:
+            return None
+        o = self._form_optimality()
+        if o["zeta"] is None:
+            return o["H_u"]
+        return tuple(hu + zt[zt.shape[0] - hu.shape[0]:] for hu, zt in zip(o["H_u"], o["zeta"]))
+
+    @property
+    def costate_defect(self):
+        """D_a / (stretch omega) + H_y + zeta_y [n_y][N] per phase: the costate equation as the NLP discretises it; NaN
+        at nodes 0, N - 1 and a node without quadrature weight.  ``None`` without multipliers."""
+        return self._optimality_or_none("defect")
+
+    def multiplier_coefficients(self, phase: int):
+        """(mu_coef [n_p][N + K - 1], zeta_coef [n_y + n_u][N + K - 1] or ``None``), laid out like the controls'."""
+        phase = self._phase(phase)
+        self._form_optimality()
+        pl, pm = self.engine.layout.phases[phase], self.engine.model.phases[phase]
+        NC = pl.N + pl.K - 1
+        mc = np.empty((pm.n_p, NC))
+        zc = np.empty((pl.n_y + pl.n_u, NC)) if self._z is not None else None
+        self._check(self._lib.pc_solution_multiplier_coefficients(self._h, phase, mc.ctypes.data if mc.size else None,
+                                                                  zc.ctypes.data if zc is not None and zc.size else None))
+        return mc, zc
+
+    def sample_optimality(self, phase: int, t=None, *, tau=None, extrapolate: bool = False):
+        """An :class:`OptimalitySample` at the Q times ``t`` (or abscissae ``tau``) of one phase.  Queries, range checks
+        and array types as in :meth:`sample`.  ``ValueError`` if the solution was made without multipliers."""
+        phase = self._phase(phase, need_handle=False)
+        if self.costate is None:
+            raise ValueError("the solution was made without multipliers: it has no path or bound multipliers")
+        return self.sample_optimality_unchecked(*self._queries(phase, t, tau, extrapolate))
+
+    def sample_optimality_unchecked(self, phase, q, flags):
+        """``pc_solution_sample_optimality`` as it is: no range check, NaN for a query outside the phase."""
+        self._form_optimality()
+        pl, pm, Q = self.engine.layout.phases[phase], self.engine.model.phases[phase], int(q.shape[0])
+        n_y, n_u = pl.n_y, pl.n_u
+        H_y, H_u, dp, mu, zeta = self._sample_into(
+            self._lib.pc_solution_sample_optimality, self._lib.pc_solution_sample_optimality_device, phase, q, flags,
+            [(n_y, Q), (n_u, Q), (n_y, Q), (pm.n_p, Q), (n_y + n_u, Q) if self._z is not None else None])
+        res, stat = dp + H_y, H_u
+        if zeta is not None:
+            res, stat = res + zeta[:n_y], H_u + zeta[n_y:]
+        return OptimalitySample(H_y=H_y, H_u=H_u, dp=dp, mu=mu, zeta=zeta, costate_residual=res, control_stationarity=stat)
+
+    def optimality_report(self, phase: int, samples_per_section: int = 33):
+        """An :class:`OptimalityReport` of one phase: ``samples_per_section`` equispaced points c in [-1, 1] of every
+        section (its two ends included; at least 2), sampled and reduced on the device."""
+        import torch
+        phase = self._phase(phase, need_handle=False)
+        if self.costate is None:
+            raise ValueError("the solution was made without multipliers: it has no path or bound multipliers")
+        m = int(samples_per_section)
+        if m < 2:
+            raise ValueError("samples_per_section must be at least 2")
+        self._phase(phase)
+        mesh, eng = self.engine.meshes[phase], self.engine
+        dev = torch.device("cuda", max(int(eng.device), 0))
+        edges = torch.as_tensor(np.asarray(mesh.tau, dtype=np.float64)[np.asarray(mesh.s)], device=dev)
+        c = torch.linspace(-1.0, 1.0, m, dtype=torch.float64, device=dev)
+        tau_q = edges[:-1, None] + 0.5 * (c[None, :] + 1.0) * (edges[1:, None] - edges[:-1, None])
+        tau_q[:, 0] = edges[:-1]
+        # an interior boundary belongs to the section on its right: a section's last sample is the double below it
+        tau_q[:, -1] = torch.nextafter(edges[1:], torch.full_like(edges[1:], -2.0))
+        tau_q[-1, -1] = edges[-1]
+        tau_q = tau_q.reshape(-1).contiguous()
+        smp = self.sample_optimality(phase, tau=tau_q)
+        t0, tF = self.initial_time[phase], self.final_time[phase]
+        time = (tau_q * (0.5 * (tF - t0)) + 0.5 * (t0 + tF)).reshape(mesh.K, m)
+
+        def reduce(a):
+            if a.shape[0] == 0:
+                return np.zeros(mesh.K), np.full(mesh.K, np.nan)
+            v = a.abs().amax(dim=0).reshape(mesh.K, m)
+            v = torch.where(torch.isnan(v), torch.full_like(v, float("inf")), v)     # a NaN sample shows as inf
+            val, idx = v.max(dim=1)
+            return val.cpu().numpy(), time.gather(1, idx[:, None])[:, 0].cpu().numpy()
+
+        cs, cs_t = reduce(smp.control_stationarity)
+        cr, cr_t = reduce(smp.costate_residual)
+        inner = lambda v: float(np.max(v[1:-1])) if mesh.K > 2 else float("nan")   # noqa: E731
+        return OptimalityReport(control_stationarity=cs, control_stationarity_time=cs_t, costate_residual=cr,
+                                costate_residual_time=cr_t, max_control_stationarity=float(np.max(cs)),
+                                max_costate_residual=float(np.max(cr)), interior_max_control_stationarity=inner(cs),
+                                interior_max_costate_residual=inner(cr), has_bound_multipliers=self._z is not None)
 
     # ---- propagation -------------------------------------------------------------------------------
     def state_scale(self, phase: int) -> np.ndarray:
