@@ -268,6 +268,14 @@ inline void check_lead(const PcPhaseArgs& a, int tail_blocks) {
                              std::to_string(a.spt) + ", tail blocks " + std::to_string(tail_blocks) + ", order " + std::to_string(un) + ")");
 }
 
+// The _w<W> kernels are compiled for a block of exactly W waves (pc_kernels.hpp: thread count, wave index and tile
+// width are constants of each replica's body), so one is planned only with that block.
+inline void check_replica_block(int wpt, int block_threads) {
+  if (wpt < 1 || block_threads != 64 * wpt)
+    throw std::runtime_error("a per-replica kernel (_w<W>) takes a block of exactly 64 W threads (waves per tile " +
+                             std::to_string(wpt) + ", block threads " + std::to_string(block_threads) + ")");
+}
+
 // ---- the argument blocks -----------------------------------------------------------------------------------------
 // Kept filled between calls; a call patches the caller's pointers, the flags, sigma and the epoch into the blocks of
 // the launches it plans and hands them over as they lie (nothing is copied, nothing allocated).
@@ -385,6 +393,7 @@ inline Plan plan(Blocks& B, const pce::Shape& S, const Have& hv, const Call& c) 
     p.last_launch |= PC_LAUNCH_MERGED;
     if (res) {
       patch(B.multi.t, c, bt, B.epoch);
+      if (hv.k[BULK_ALL_RES_W]) check_replica_block(S.wpt_all, bt);
       p.add(hv.k[BULK_ALL_RES_W] ? BULK_ALL_RES_W : BULK_ALL_RES, 0, nb + m.tail_blocks, bt, std::max(S.lds_all, S.tail_lds_bytes),
             &B.multi, sizeof(B.multi));
       p.last_launch |= PC_LAUNCH_RESIDENT | (m.tail_blocks << PC_LAUNCH_TAIL_BLOCKS_SHIFT) | ((bt / 64) << PC_LAUNCH_TAIL_WAVES_SHIFT);
@@ -395,6 +404,7 @@ inline Plan plan(Blocks& B, const pce::Shape& S, const Have& hv, const Call& c) 
     const int bt = S.TB * S.ph[0].wpt, ntb = S.tail_blocks;
     patch(B.res.b, c, B.epoch, ntb);
     patch(B.res.t, c, bt, B.epoch);
+    if (hv.k[BULK_RES_W]) check_replica_block(B.res.b.a.wpt, bt);
     p.add(hv.k[BULK_RES_W] ? BULK_RES_W : BULK_RES, 0, S.ph[0].n_tiles + ntb, bt, std::max(S.ph[0].lds_bytes, S.tail_lds_bytes), &B.res,
           sizeof(B.res));
     p.last_launch = PC_LAUNCH_RESIDENT | (ntb << PC_LAUNCH_TAIL_BLOCKS_SHIFT) | ((bt / 64) << PC_LAUNCH_TAIL_WAVES_SHIFT);

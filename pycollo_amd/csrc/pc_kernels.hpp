@@ -25,6 +25,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 
@@ -455,31 +456,123 @@ struct BulkIn {
   int64_t hoff[3 * St::NZ + St::NS * St::NZ > 0 ? 3 * St::NZ + St::NS * St::NZ : 1];
 };
 
-#define PC_PIN(v) asm volatile("" ::"s"(v))
 #ifndef PC_PIN_BUDGET
 #define PC_PIN_BUDGET 40   // SGPRs the per-variable constants may take
 #endif
-// One empty asm per value would do the forcing too, but every inline asm is a scheduling boundary: the loads
-// then come in several dependent batches (measured: 6 loads, wait, 2 loads, wait, 2 loads, wait ...).  Folding all
-// values into one word that a single asm consumes leaves the scheduler free to issue every load at once.
-struct PinAcc {
-  unsigned long long h = 0;
-  template <class T>
-  __device__ __forceinline__ void operator()(T* v) { h ^= (unsigned long long)reinterpret_cast<uintptr_t>(v); }
-  __device__ __forceinline__ void operator()(double v) { h ^= __builtin_bit_cast(unsigned long long, v); }
-  __device__ __forceinline__ void operator()(long long v) { h ^= (unsigned long long)v; }
-  __device__ __forceinline__ void operator()(long v) { h ^= (unsigned long long)v; }
-  __device__ __forceinline__ void operator()(int v) { h ^= (unsigned long long)(unsigned)v; }
-  __device__ __forceinline__ void done() const { asm volatile("" ::"s"(h)); }
-};
-template <class T, int N, int... I>
-__device__ __forceinline__ void pin_array_impl(PinAcc& p, const T (&a)[N], std::integer_sequence<int, I...>) {
-  (p(a[I]), ...);
+// Pinning: a group of uniform values is forced into SGPRs at one point by ONE empty asm that takes every value of
+// the group as an "s" operand of its own -- no instruction is issued for it.  One asm per VALUE would do the forcing
+// too, but every inline asm is a scheduling boundary: the loads then come in several dependent batches (measured: 6
+// loads, wait, 2 loads, wait, 2 loads, wait ...); with one asm per group the scheduler is free to issue every scalar
+// load of the group ahead of a single wait.  (An earlier form folded the values with XOR into one word for the asm:
+// the same freedom, at 40-odd scalar instructions per wave that computed nothing.)
+// CLOBBER: the asm also clobbers "memory", for a group with vector loads written in front of it (the table loads of
+// the kernels with preloaded lead scalars): they are then issued in front of the wait the asm implies and not moved
+// behind it, a scalar-cache round trip late.
+// A group is a std::tuple built from pin_vals / pin_if / pin_array / pin_array_where and handed to pin_group; an asm
+// takes at most 30 operands, which bounds a group.
+template <class T>
+__device__ __forceinline__ uintptr_t pin_word(T* v) { return reinterpret_cast<uintptr_t>(v); }
+__device__ __forceinline__ unsigned long long pin_word(double v) { return __builtin_bit_cast(unsigned long long, v); }
+__device__ __forceinline__ long long pin_word(long long v) { return v; }
+__device__ __forceinline__ long pin_word(long v) { return v; }
+__device__ __forceinline__ int pin_word(int v) { return v; }
+template <class... T>
+__device__ __forceinline__ auto pin_vals(const T&... v) { return std::make_tuple(pin_word(v)...); }
+template <bool C, class... T>
+__device__ __forceinline__ auto pin_if(const T&... v) {   // (C false: the values are not even read)
+  if constexpr (C) return pin_vals(v...);
+  else return std::tuple<>{};
+}
+template <class Pred, class T, int N, int... I>
+__device__ __forceinline__ auto pin_array_impl(const T (&a)[N], std::integer_sequence<int, I...>) {
+  return std::tuple_cat(pin_if<Pred::test(I)>(a[I])...);
+}
+struct PinEvery { static constexpr bool test(int) { return true; } };
+// the first CNT entries of an array, or those of them Pred::test(index) picks
+template <int CNT, class Pred, class T, int N>
+__device__ __forceinline__ auto pin_array_where(const T (&a)[N]) {
+  return pin_array_impl<Pred>(a, std::make_integer_sequence<int, CNT>{});
 }
 template <int CNT, class T, int N>
-__device__ __forceinline__ void pin_array(PinAcc& p, const T (&a)[N]) {
-  pin_array_impl(p, a, std::make_integer_sequence<int, CNT>{});
+__device__ __forceinline__ auto pin_array(const T (&a)[N]) { return pin_array_where<CNT, PinEvery>(a); }
+#define PC_PIN_OP(i) "s"(std::get<i>(g))
+#define PC_PIN_OPS_1 PC_PIN_OP(0)
+#define PC_PIN_OPS_2 PC_PIN_OPS_1, PC_PIN_OP(1)
+#define PC_PIN_OPS_3 PC_PIN_OPS_2, PC_PIN_OP(2)
+#define PC_PIN_OPS_4 PC_PIN_OPS_3, PC_PIN_OP(3)
+#define PC_PIN_OPS_5 PC_PIN_OPS_4, PC_PIN_OP(4)
+#define PC_PIN_OPS_6 PC_PIN_OPS_5, PC_PIN_OP(5)
+#define PC_PIN_OPS_7 PC_PIN_OPS_6, PC_PIN_OP(6)
+#define PC_PIN_OPS_8 PC_PIN_OPS_7, PC_PIN_OP(7)
+#define PC_PIN_OPS_9 PC_PIN_OPS_8, PC_PIN_OP(8)
+#define PC_PIN_OPS_10 PC_PIN_OPS_9, PC_PIN_OP(9)
+#define PC_PIN_OPS_11 PC_PIN_OPS_10, PC_PIN_OP(10)
+#define PC_PIN_OPS_12 PC_PIN_OPS_11, PC_PIN_OP(11)
+#define PC_PIN_OPS_13 PC_PIN_OPS_12, PC_PIN_OP(12)
+#define PC_PIN_OPS_14 PC_PIN_OPS_13, PC_PIN_OP(13)
+#define PC_PIN_OPS_15 PC_PIN_OPS_14, PC_PIN_OP(14)
+#define PC_PIN_OPS_16 PC_PIN_OPS_15, PC_PIN_OP(15)
+#define PC_PIN_OPS_17 PC_PIN_OPS_16, PC_PIN_OP(16)
+#define PC_PIN_OPS_18 PC_PIN_OPS_17, PC_PIN_OP(17)
+#define PC_PIN_OPS_19 PC_PIN_OPS_18, PC_PIN_OP(18)
+#define PC_PIN_OPS_20 PC_PIN_OPS_19, PC_PIN_OP(19)
+#define PC_PIN_OPS_21 PC_PIN_OPS_20, PC_PIN_OP(20)
+#define PC_PIN_OPS_22 PC_PIN_OPS_21, PC_PIN_OP(21)
+#define PC_PIN_OPS_23 PC_PIN_OPS_22, PC_PIN_OP(22)
+#define PC_PIN_OPS_24 PC_PIN_OPS_23, PC_PIN_OP(23)
+#define PC_PIN_OPS_25 PC_PIN_OPS_24, PC_PIN_OP(24)
+#define PC_PIN_OPS_26 PC_PIN_OPS_25, PC_PIN_OP(25)
+#define PC_PIN_OPS_27 PC_PIN_OPS_26, PC_PIN_OP(26)
+#define PC_PIN_OPS_28 PC_PIN_OPS_27, PC_PIN_OP(27)
+#define PC_PIN_OPS_29 PC_PIN_OPS_28, PC_PIN_OP(28)
+#define PC_PIN_OPS_30 PC_PIN_OPS_29, PC_PIN_OP(29)
+#define PC_PIN_CASE(n)                                                        \
+  if constexpr (NV == n) {                                                    \
+    if constexpr (CLOBBER) asm volatile("" ::PC_PIN_OPS_##n : "memory");      \
+    else asm volatile("" ::PC_PIN_OPS_##n);                                   \
+  }
+template <bool CLOBBER = false, class... T>
+__device__ __forceinline__ void pin_group(const std::tuple<T...>& g) {
+  constexpr int NV = (int)sizeof...(T);
+  static_assert(NV <= 30, "an inline asm takes at most 30 operands: split the group");
+  PC_PIN_CASE(1); PC_PIN_CASE(2); PC_PIN_CASE(3); PC_PIN_CASE(4); PC_PIN_CASE(5); PC_PIN_CASE(6);
+  PC_PIN_CASE(7); PC_PIN_CASE(8); PC_PIN_CASE(9); PC_PIN_CASE(10); PC_PIN_CASE(11); PC_PIN_CASE(12);
+  PC_PIN_CASE(13); PC_PIN_CASE(14); PC_PIN_CASE(15); PC_PIN_CASE(16); PC_PIN_CASE(17); PC_PIN_CASE(18);
+  PC_PIN_CASE(19); PC_PIN_CASE(20); PC_PIN_CASE(21); PC_PIN_CASE(22); PC_PIN_CASE(23); PC_PIN_CASE(24);
+  PC_PIN_CASE(25); PC_PIN_CASE(26); PC_PIN_CASE(27); PC_PIN_CASE(28); PC_PIN_CASE(29); PC_PIN_CASE(30);
 }
+#undef PC_PIN_CASE
+#undef PC_PIN_OP
+#undef PC_PIN_OPS_1
+#undef PC_PIN_OPS_2
+#undef PC_PIN_OPS_3
+#undef PC_PIN_OPS_4
+#undef PC_PIN_OPS_5
+#undef PC_PIN_OPS_6
+#undef PC_PIN_OPS_7
+#undef PC_PIN_OPS_8
+#undef PC_PIN_OPS_9
+#undef PC_PIN_OPS_10
+#undef PC_PIN_OPS_11
+#undef PC_PIN_OPS_12
+#undef PC_PIN_OPS_13
+#undef PC_PIN_OPS_14
+#undef PC_PIN_OPS_15
+#undef PC_PIN_OPS_16
+#undef PC_PIN_OPS_17
+#undef PC_PIN_OPS_18
+#undef PC_PIN_OPS_19
+#undef PC_PIN_OPS_20
+#undef PC_PIN_OPS_21
+#undef PC_PIN_OPS_22
+#undef PC_PIN_OPS_23
+#undef PC_PIN_OPS_24
+#undef PC_PIN_OPS_25
+#undef PC_PIN_OPS_26
+#undef PC_PIN_OPS_27
+#undef PC_PIN_OPS_28
+#undef PC_PIN_OPS_29
+#undef PC_PIN_OPS_30
 
 // UN > 0: the phase's mesh has UN nodes in every section and the kernel is compiled for exactly that
 // order (loops over section rows / nodes unroll, their LDS reads issue back to back, index arithmetic
@@ -545,11 +638,12 @@ __device__ __forceinline__ int xcd_major(int b, int nb) {
 #ifndef PC_STAMPS_WAVES
 #define PC_STAMPS_WAVES 16384
 #endif
-extern "C" __device__ unsigned long long pc_stamps[PC_STAMPS_WAVES * 24];
+#define PC_STAMPS_STRIDE 32   // words per wave (tools/stamps.py reads the same)
+extern "C" __device__ unsigned long long pc_stamps[PC_STAMPS_WAVES * PC_STAMPS_STRIDE];
 #define PC_STAMP(i)                                                                                         \
   do {                                                                                                      \
     if ((threadIdx.x & 63) == 0 && pc_stamp_slot < PC_STAMPS_WAVES)                                         \
-      pc_stamps[(size_t)pc_stamp_slot * 24 + (i)] = (i) == 9 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime(); \
+      pc_stamps[(size_t)pc_stamp_slot * PC_STAMPS_STRIDE + (i)] = (i) == 9 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime(); \
   } while (0)
 #else
 #define PC_STAMP(i) do { } while (0)
@@ -628,7 +722,13 @@ __device__ __forceinline__ void bulk(const PcPhaseArgs& KA, bool MULTI = false, 
     n1 = A.tile_n0[tile + 1];
   }
   const int T = n1 - n0;                 // defect rows per state in this tile; nodes n0 .. n0+T
+  // Per-replica builds (WN > 0) know the block's shape at compile time: the host plans a _w<W> kernel only with
+  // 64 W threads (pcl::plan), and the entry has dispatched on the wave index, so this is wave WIDX of the workgroup:
+  // tid = 64 WIDX + lane.  Said as an assumption about the hardware's index, not rebuilt from the lane (which takes a
+  // register of its own next to it).  Every `tid < table length` a replica can never satisfy, the strided continuation
+  // of the staging loops and the run-time test in front of every barrier then fold away.
   const int tid = threadIdx.x;
+  if constexpr (WN > 0) __builtin_assume((tid >> 6) == WIDX);
   const int W = WN > 0 ? WN : A.wpt;                          // 1, 2 or 4
   const int t = W > 1 ? (tid & 63) : tid;                     // node slot of this lane inside its replica
   const bool active = t <= T;
@@ -683,10 +783,12 @@ __device__ __forceinline__ void bulk(const PcPhaseArgs& KA, bool MULTI = false, 
   // pointers have arrived anyway and fewer values are live across it (Delta III and the any-order kernels lose 2 %
   // with the early form).
   const bool wantH = A.flags & PC_FLAG_H;
-  const int TB = A.block_threads;   // (blockDim.x is a separate, late scalar load)
+  const int TB = WN > 0 ? 64 * WN : A.block_threads;   // (blockDim.x is a separate, late scalar load)
   const bool has_prev = k0 > 0;
   const int kp = has_prev ? k0 - 1 : 0;  // first staged section
   const int nsec = k1 - kp;              // staged sections (previous one included)
+  // a replica's tile has at most 64 nodes, hence at most 63 sections of its own next to the previous one
+  if constexpr (WN > 0) __builtin_assume(nsec <= 65);
   constexpr int QA_N = UN > 0 ? (UN - 1) * UN : 0;   // a compile-time order stages just its own A_n and w_n, at the
   double r_h = 0.0, r_qa = 0.0, r_qw = 0.0;          // start of the LDS table areas (QAO = QWO = 0)
   const bool odd_prev = PURE && has_prev && r_nprev != UN;   // (wave-uniform)
@@ -704,6 +806,8 @@ __device__ __forceinline__ void bulk(const PcPhaseArgs& KA, bool MULTI = false, 
       lam0 = A.sec_s[kp];
     }
     lam_cnt = n1 - lam0;
+    // (the tile's own rows, at most 63, and the previous section's: one chunk and a few lanes of wave 1)
+    if constexpr (WN > 0) __builtin_assume(lam_cnt <= 64 + PC_MAX_ORDER - 2);
     if (wantH) {
       // one predicated block per chunk for all states (a select per load is an exec-mask save / restore and a branch
       // around each one: 2 NY of them here and again at the LDS stores below)
@@ -733,47 +837,39 @@ __device__ __forceinline__ void bulk(const PcPhaseArgs& KA, bool MULTI = false, 
   // Two groups.  The first is what the per-node loads and the table staging need (pointers, offsets, geometry);
   // the second -- output pointers, scaling constants, run offsets -- is consumed by a second asm placed after those
   // loads have been issued, so that its scalar-load round trip overlaps their latency instead of preceding it.
-  PinAcc pin;
-  pin(A.x); pin(A.lam); pin(A.sec_h); pin(A.qa); pin(A.qw);
-  pin(A.x_off); pin(A.c_off); pin(A.N); pin(A.K); pin(A.flags); pin(A.qa_total); pin(A.qw_total); pin(A.tile_begin);
-  pin(A.uni_n); pin(A.spt); pin(A.lds_out); pin(A.wpt); pin(A.n_blocks); pin(A.block_threads);
-  if constexpr (UN > 0) { pin(A.qa0); pin(A.qwabs); }
-  if constexpr (NP > 0) pin(A.c_path_off);
-  if constexpr (NQ > 0) pin(A.c_int_off);
-  if constexpr (NS > 0) pin(A.s_off);
-  if constexpr (UN == 0) { pin(A.tile_k0); pin(A.tile_n0); pin(A.sec_s); pin(A.sec_E); }   // any-mesh tables
-  pin.done();
+  const auto first_group = std::tuple_cat(
+      pin_vals(A.x, A.lam, A.sec_h, A.qa, A.qw, A.x_off, A.c_off, A.N, A.K, A.flags, A.qa_total, A.qw_total, A.tile_begin,
+               A.uni_n, A.spt, A.lds_out, A.wpt, A.n_blocks, A.block_threads),
+      pin_if<(UN > 0)>(A.qa0, A.qwabs), pin_if<(NP > 0)>(A.c_path_off), pin_if<(NQ > 0)>(A.c_int_off), pin_if<(NS > 0)>(A.s_off),
+      pin_if<UN == 0>(A.tile_k0, A.tile_n0, A.sec_s, A.sec_E));   // any-mesh tables
+  if (early_aux) pin_group<true>(first_group);   // (the table loads above stay above; `early_aux` is a constant of the build)
+  else pin_group(first_group);
   // (hslot0 / hslotN are left lazy: only the two edge tiles read them)
   constexpr int NHO = 3 * NZ + NS * NZ;
   constexpr bool PINNED = 2 * (St::NSCAL + NFN + NHO) <= PC_PIN_BUDGET;
+  // the scaling entries the bulk kernel reads: V, r of z, of the free times and of s; the row weights.  (V, r
+  // of the integral variables belong to the tail kernel.)
+  struct ScalUsed {
+    static constexpr bool test(int i) {
+      return (i < St::O_VQ) || (i >= St::O_VT && i < St::O_VT + St::NT) || (i >= St::O_RT && i < St::O_RT + St::NT) || (i >= St::O_VS);
+    }
+  };
+  struct HoffUsed {   // t strips only with free times
+    static constexpr bool test(int i) { return i < St::NZ || (St::NT > 0 && i < 3 * St::NZ) || i >= 3 * St::NZ; }
+  };
   auto pin_second_group = [&]() {
-    PinAcc pin2;
-    pin2(A.c); pin2(A.G); pin2(A.H);
-    if constexpr (NRED > 0) { if constexpr (RES) pin2(A.gran); else pin2(A.partials); }
-    if constexpr (!M::T0_FREE) pin2(A.t_fixed[0]);
-    if constexpr (!M::TF_FREE) pin2(A.t_fixed[1]);
+    auto outs = std::tuple_cat(pin_vals(A.c, A.G, A.H), pin_if<(NRED > 0 && RES)>(A.gran), pin_if<(NRED > 0 && !RES)>(A.partials),
+                               pin_if<!M::T0_FREE>(A.t_fixed[0]), pin_if<!M::TF_FREE>(A.t_fixed[1]));
     // The per-variable constants (scaling, run offsets) are hoisted too while they fit the scalar register file
     // next to the above.  A model with many variables would have them spilled to VGPR lanes (the shuttle kernel
     // carried 2000 v_readlane, whole 16-register tuples reloaded per use): such a model reads them from an LDS
     // copy instead (uniform-address ds_read, staged with the quadrature tables).
     if constexpr (PINNED) {
-      // the scaling entries the bulk kernel reads: V, r of z, of the free times and of s; the row weights.  (V, r
-      // of the integral variables belong to the tail kernel.)
-      static_for<0, St::NSCAL>([&](auto i_) {
-        constexpr int i = decltype(i_)::value;
-        constexpr bool used = (i < St::O_VQ) || (i >= St::O_VT && i < St::O_VT + NT) || (i >= St::O_RT && i < St::O_RT + NT) ||
-                              (i >= St::O_VS);
-        if constexpr (used) pin2(A.scal[i]);
-      });
-      pin_array<NFN>(pin2, A.goff);
-      static_for<0, NHO>([&](auto i_) {
-        constexpr int i = decltype(i_)::value;
-        if constexpr (i < NZ || (NT > 0 && i < 3 * NZ) || i >= 3 * NZ) pin2(A.hoff[i]);   // t strips only with free times
-      });
+      pin_group(std::tuple_cat(outs, pin_array_where<St::NSCAL, ScalUsed>(A.scal), pin_array<NFN>(A.goff),
+                               pin_array_where<NHO, HoffUsed>(A.hoff)));
     } else {
-      pin2(A.tab);
+      pin_group(std::tuple_cat(outs, pin_vals(A.tab)));
     }
-    pin2.done();
   };
 
   extern __shared__ double smem[];
@@ -883,6 +979,7 @@ __device__ __forceinline__ void bulk(const PcPhaseArgs& KA, bool MULTI = false, 
     r_qw = tid < A.qw_total ? A.qw[tid] : 0.0;
   }
   pin_second_group();
+  PC_STAMP(24);   // prologue issued: every load is out, the first wait for a vector load (in order: the node values') is next
   if (!uni) {
     for (int i = tid; i <= nsec; i += TB) {
       s_s[i] = A.sec_s[kp + i];

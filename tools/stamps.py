@@ -18,6 +18,9 @@ NAMES = ["0 wave starts", "1 node values arrived", "2 node functions (first pass
          "7 instruction stream done", "8 own stores drained"]
 
 
+STRIDE = 32   # words per wave (PC_STAMPS_STRIDE, pc_kernels.hpp)
+
+
 def xcd_major(b, nb):
     q, r, x, j = nb // 8, nb % 8, b % 8, b // 8
     return x * q + np.minimum(x, r) + j
@@ -104,7 +107,7 @@ def main():
         st = None
         for part in range(8):   # a code object in parts: the stamps are in the part whose kernel ran
             try:
-                cand = eng.read_symbol(f"pc_stamps@{part}", np.uint64, n_waves * 24).reshape(n_waves, 24).astype(np.int64)
+                cand = eng.read_symbol(f"pc_stamps@{part}", np.uint64, n_waves * STRIDE).reshape(n_waves, STRIDE).astype(np.int64)
             except RuntimeError:
                 break
             if st is None or np.count_nonzero(cand[:, 0]) > np.count_nonzero(st[:, 0]):
@@ -135,6 +138,13 @@ def main():
         d = rel[:, i] - rel[:, prev]
         print(f"{names[i - 1]:58s} {np.median(d):8.0f} {np.percentile(d, 10):8.0f} {np.percentile(d, 90):8.0f} {np.median(d) / np.median(life):6.1%}")
         prev = i
+    # stamp 24 sits before the first wait for a vector load: what is left of phase 0-1 behind it is load latency
+    if np.any(live[:, 24] > 0):
+        m = live[:, 24] > 0
+        issued, arrived = (live[m, 24] - live[m, 0]), (live[m, 1] - live[m, 24])
+        print(f"phase 0-1 split: prologue issued after {np.median(issued):.0f} ticks (p10 {np.percentile(issued, 10):.0f}, p90 "
+              f"{np.percentile(issued, 90):.0f}); node values arrive {np.median(arrived):.0f} ticks later (p10 {np.percentile(arrived, 10):.0f}, "
+              f"p90 {np.percentile(arrived, 90):.0f})")
     if args.refined and any(eng.mixed):
         by_order(eng, prob, live, np.concatenate(slots), W, len(rows))
     # per defect state (stamps 10 + 2a: block produced into LDS, 11 + 2a: read back and stores issued), over the waves
