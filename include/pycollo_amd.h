@@ -658,6 +658,34 @@ int pc_solution_propagate_device(pc_solution* sol, int phase, int64_t n_seg, con
                                  const double* atol, int64_t max_steps, double* d_y_arrive, int32_t* d_accepted,
                                  int32_t* d_rejected, int32_t* d_seg_status);
 
+/* ---- propagation with integrals and dense output (no reference counterpart) ----
+ * pc_solution_propagate's segments, steps and step control, and beside the state the phase's n_q integrals I_m with
+ * dI_m/dc = stretch (w_k / 2) g_m(y, u(c), q, t0, tF, s), I = 0 at every segment's first node, by the same tableau.
+ * integral_atol: null -- the integrals take no part in the error norm, and y_arrive, accepted, rejected and seg_status
+ * are what pc_solution_propagate returns, to the bit -- or [n_q] finite positive entries (always checked): integral m
+ * adds |e_m| / (integral_atol_m + rtol max(|I_m|, |I_m,new|)) to the maximum (no effect with substeps >= 1).
+ * tau_q [n_query]: query abscissae, any order, duplicates allowed, each finite and inside [tau_0, tau_{N-1}] = [-1, 1]
+ * (anything else fails before the launch: a propagated path is not extrapolated); n_query = 0 is allowed.  A query
+ * belongs to the node interval (tau_j, tau_{j+1}] that holds it (tau_0: to the first) and is answered by the first
+ * accepted step of that interval whose end reaches it, by Shampine's continuous extension of the pair: y + h sum_i K_i
+ * b_i(theta), theta = (c_q - c) / h; a query at the step's end gets the step's new state itself, so the node abscissae
+ * return y_arrive and q_arrive to the bit (a restart node: the arriving value).  Queries behind the last accepted step
+ * of an interval that used up max_steps, and in every later interval of that segment, are NaN.
+ * Outputs as in pc_solution_propagate, and q_arrive [n_q][N] (column 0: 0), y_dense [n_y][n_query], q_dense
+ * [n_q][n_query] in the caller's query order.  Runs pc_sol_propagate_dense_p<i> on the handle's stream.  Host pointers
+ * for the outputs; synchronises. */
+int pc_solution_propagate_dense(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
+                                const double* atol, const double* integral_atol, int64_t max_steps, int64_t n_query,
+                                const double* tau_q, double* y_arrive, int32_t* accepted, int32_t* rejected, int32_t* seg_status,
+                                double* q_arrive, double* y_dense, double* q_dense);
+/* the same with device pointers for the seven outputs (seg_nodes, atol, integral_atol and tau_q stay host arrays: they are
+ * checked, sorted and staged before the launch); queued on the handle's stream, does not synchronise behind the launch */
+int pc_solution_propagate_dense_device(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps,
+                                       double rtol, const double* atol, const double* integral_atol, int64_t max_steps,
+                                       int64_t n_query, const double* tau_q, double* d_y_arrive, int32_t* d_accepted,
+                                       int32_t* d_rejected, int32_t* d_seg_status, double* d_q_arrive, double* d_y_dense,
+                                       double* d_q_dense);
+
 /* timing of the last n pc_eval_all_device launches is measured by the caller with HIP events on the
  * stream it passed; this returns the stream the handle owns (hipStream_t) */
 void* pc_stream(pc_handle* h);

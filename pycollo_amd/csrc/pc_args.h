@@ -496,4 +496,32 @@ struct PcSolPropagateArgs {
   int32_t n_seg, substeps, max_steps, reserved;   // substeps 0: adaptive
 };
 
+// Arguments of the propagation with integrals and dense output (pc_solution.hpp, pc_sol_propagate_dense):
+// the lane of PcSolPropagateArgs carries the NQ integrals of the phase beside the state and answers the queries its
+// node intervals own.  The queries are sorted by tau on the host (pc_propagate_plan.hpp): sorted query k is the
+// caller's query q_order[k]; slot 0 (sorted queries node_q0[0] .. node_q0[1]) holds the queries at tau_0, slot j >= 1
+// (node_q0[j] .. node_q0[j+1]) those in (tau_{j-1}, tau_j], answered by the lane that integrates that interval.
+struct PcSolPropagateDenseArgs {
+  PcPhaseView v;
+  PcSolCurves c;
+  const double* tau;           // [N]
+  const int32_t* seg_node;     // [n_seg+1]
+  const int32_t* seg_sec;      // [n_seg]
+  const double* atol;          // [NY]
+  const double* integral_atol; // [NQ], or null: the integrals take no part in the error norm
+  const double* tau_q;         // [Q] the queries' tau, ascending
+  const int32_t* q_order;      // [Q] the caller's index of sorted query k
+  const int32_t* node_q0;      // [N+1]
+  double* y_arrive;            // [NY][N] as in PcSolPropagateArgs, like the next three
+  int32_t* accepted;           // [N]
+  int32_t* rejected;           // [N]
+  int32_t* seg_status;         // [n_seg]
+  double* q_arrive;            // [NQ][N] column j >= 1: the segment's integral arriving at node j; column 0: 0
+  double* y_dense;             // [NY][Q] in the caller's query order
+  double* q_dense;             // [NQ][Q]
+  double rtol;
+  int64_t Q;
+  int32_t n_seg, substeps, max_steps, reserved;
+};
+
 #endif  // PC_ARGS_H

@@ -1,11 +1,15 @@
 // Forward propagation of an NLP point: the host-side index arithmetic of pc_sol_propagate (compiles without HIP;
 // tests/c/propagate_plan_sanitize.cpp runs it under AddressSanitizer + UBSan).  The checks of the segment list and of
 // the tolerances, the first section of every segment and the grid.  The sections are the fit kernel's
-// (pc_solution_plan.hpp).
+// (pc_solution_plan.hpp).  For pc_sol_propagate_dense also the check of integral_atol and the queries: their
+// checks, their stable sort and the slot of every query (tests/c/propagate_dense_plan_sanitize.cpp).
 #ifndef PC_PROPAGATE_PLAN_HPP
 #define PC_PROPAGATE_PLAN_HPP
 
+#include <algorithm>
+#include <climits>
 #include <cmath>
+#include <cstdint>
 
 #include "pc_solution_plan.hpp"
 
@@ -50,6 +54,57 @@ inline PropagatePlan build_propagate_plan(const FitPlan& F, int64_t n_seg, const
   }
   P.blocks = (n_seg + TB - 1) / TB;
   return P;
+}
+
+// ---- integrals and dense output (pc_sol_propagate_dense) ----
+// integral_atol: null (the integrals take no part in the error norm), or one finite positive entry per integral
+inline void check_integral_atol(const double* integral_atol, int NQ) {
+  if (NQ < 0) throw std::runtime_error("propagate: negative integral count");
+  if (!integral_atol) return;
+  for (int m = 0; m < NQ; ++m)
+    if (!(std::isfinite(integral_atol[m]) && integral_atol[m] > 0.0))
+      throw std::runtime_error("propagate: every integral_atol must be finite and positive");
+}
+
+// The queries of a dense propagation, sorted.  Slot 0 holds the queries at tau_0; slot j >= 1 those in (tau_{j-1},
+// tau_j]: a query on a node belongs to the interval that ends there.  Slot j is the sorted queries node_q0[j] ..
+// node_q0[j+1]; sorted query k is the caller's query q_order[k] (a stable sort: equal queries keep the caller's order).
+struct DenseQueryPlan {
+  int64_t Q = 0;
+  std::vector<int32_t> q_order;    // [Q]
+  std::vector<int32_t> node_q0;    // [N+1] ascending, node_q0[0] = 0, node_q0[N] = Q
+  std::vector<double> tau_sorted;  // [Q] ascending
+};
+
+// node_tau [N] strictly ascending.  Refused: a query that is NaN, infinite or outside [tau_0, tau_{N-1}] (a propagated
+// path is not extrapolated), Q < 0, Q >= 2^31, a null array with Q > 0.
+inline DenseQueryPlan build_dense_query_plan(int N, const double* node_tau, int64_t Q, const double* tau_q) {
+  if (N < 2 || !node_tau) throw std::runtime_error("propagate: the phase has no node interval");
+  if (Q < 0 || Q > (int64_t)INT32_MAX) throw std::runtime_error("propagate: the number of queries must be in [0, 2^31)");
+  if (Q > 0 && !tau_q) throw std::runtime_error("propagate: null queries");
+  for (int64_t q = 0; q < Q; ++q) {
+    if (!std::isfinite(tau_q[q])) throw std::runtime_error("propagate: a query is not finite");
+    if (!(tau_q[q] >= node_tau[0] && tau_q[q] <= node_tau[N - 1])) throw std::runtime_error("propagate: a query lies outside the phase");
+  }
+  DenseQueryPlan D;
+  D.Q = Q;
+  D.q_order.resize((size_t)Q);
+  for (int64_t q = 0; q < Q; ++q) D.q_order[(size_t)q] = (int32_t)q;
+  std::stable_sort(D.q_order.begin(), D.q_order.end(), [&](int32_t a, int32_t b) { return tau_q[a] < tau_q[b]; });
+  D.tau_sorted.resize((size_t)Q);
+  D.node_q0.assign((size_t)N + 1, 0);
+  for (int64_t k = 0; k < Q; ++k) {
+    const double t = tau_q[D.q_order[(size_t)k]];
+    D.tau_sorted[(size_t)k] = t;
+    int lo = 0, hi = N - 1;   // the first node j with t <= tau_j (t <= tau_{N-1} was checked)
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (t <= node_tau[mid]) hi = mid; else lo = mid + 1;
+    }
+    ++D.node_q0[(size_t)lo + 1];
+  }
+  for (int j = 0; j < N; ++j) D.node_q0[(size_t)j + 1] += D.node_q0[(size_t)j];
+  return D;
 }
 
 }  // namespace pcs

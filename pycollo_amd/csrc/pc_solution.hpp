@@ -646,15 +646,34 @@ __host__ __device__ constexpr double dp_e(int s) {
   return t[s];
 }
 
-// One step of width h from (c, y) in the section whose coefficients start at off (n of them per control); g = stretch
-// w_k / 2.  v holds the q / t / s arguments of f behind NZ.  ynew: the fifth-order solution.  ERR: the seventh stage
-// and err, the scaled error norm (bad: it is not finite).
-template <class M, bool ERR>
-__device__ __forceinline__ void prop_step(const PcSolPropagateArgs& A, double* v, const double* y, int64_t off, int n, double c,
-                                          double h, double g, double* ynew, double& err, bool& bad) {
+// Shampine's continuous extension of the pair (SIAM J. Numer. Anal. 23, 1986): over an accepted step the value at
+// c + theta h is y + h sum_i K_i b_i(theta), b_i(theta) = theta (P[i][0] + theta (P[i][1] + theta (P[i][2] + theta P[i][3])));
+// b_i(1) = b_i.  Row 1 is zero, as b_1 is.
+__host__ __device__ constexpr double dp_p(int s, int i) {
+  constexpr double t[7][4] = {
+      {1.0, -8048581381.0 / 2820520608.0, 8663915743.0 / 2820520608.0, -12715105075.0 / 11282082432.0},
+      {0.0, 0.0, 0.0, 0.0},
+      {0.0, 131558114200.0 / 32700410799.0, -68118460800.0 / 10900136933.0, 87487479700.0 / 32700410799.0},
+      {0.0, -1754552775.0 / 470086768.0, 14199869525.0 / 1410260304.0, -10690763975.0 / 1880347072.0},
+      {0.0, 127303824393.0 / 49829197408.0, -318862633887.0 / 49829197408.0, 701980252875.0 / 199316789632.0},
+      {0.0, -282668133.0 / 205662961.0, 2019193451.0 / 616988883.0, -1453857185.0 / 822651844.0},
+      {0.0, 40617522.0 / 29380423.0, -110615467.0 / 29380423.0, 69997945.0 / 29380423.0}};
+  return t[s][i];
+}
+__host__ __device__ constexpr bool dp_p_row(int s) {
+  return dp_p(s, 0) != 0.0 || dp_p(s, 1) != 0.0 || dp_p(s, 2) != 0.0 || dp_p(s, 3) != 0.0;
+}
+
+// The stages of one step of width h from (c, y) in the section whose coefficients start at off (n of them per
+// control); g = stretch w_k / 2.  v holds the q / t / s arguments of f behind NZ.  Ks: the stages g f; ynew: the
+// fifth-order solution.  The seventh stage (f at ynew) is evaluated with ERR, or when stage7 says so.  NG > 0: the NG
+// integrals I ride along -- Gs: the stages g g_m at the same arguments (M::eval_fg), Inew by the same row and order.
+template <class M, bool ERR, int NG, class Args>
+__device__ __forceinline__ void prop_stages(const Args& A, double* v, const double* y, const double* I, int64_t off, int n, double c,
+                                            double h, double g, bool stage7, double (&Ks)[7][S<M>::NY > 0 ? S<M>::NY : 1],
+                                            double (&Gs)[7][NG > 0 ? NG : 1], double* ynew, double* Inew) {
   using St = S<M>;
   constexpr int NY = St::NY, NU = St::NU, NY1 = NY > 0 ? NY : 1;
-  double Ks[7][NY1];
   static_for<0, 7>([&](auto s_) {
     constexpr int s = decltype(s_)::value;
     // the stage's state: y + h sum_i a[s][i] K_i, i ascending, zero entries of the tableau left out
@@ -669,7 +688,18 @@ __device__ __forceinline__ void prop_step(const PcSolPropagateArgs& A, double* v
       v[a] = s == 0 ? y[a] : y[a] + h * acc;
       if constexpr (s == 6) ynew[a] = v[a];
     });
-    if constexpr (s < 6 || ERR) {
+    if constexpr (s == 6)
+      static_for<0, NG>([&](auto m_) {
+        constexpr int m = decltype(m_)::value;
+        double acc = 0.0;
+        static_for<0, 6>([&](auto i_) {
+          constexpr int i = decltype(i_)::value;
+          constexpr double w = dp_a(6, i);
+          if constexpr (w != 0.0) acc += w * Gs[i][m];
+        });
+        Inew[m] = I[m] + h * acc;
+      });
+    if (s < 6 || ERR || stage7) {
       constexpr double cs = dp_c(s);
       const double cc = s == 0 ? c : c + cs * h;
       static_for<0, NU>([&](auto b_) {
@@ -679,23 +709,49 @@ __device__ __forceinline__ void prop_step(const PcSolPropagateArgs& A, double* v
       double F[NY1];
       M::eval_f(v, F);
       static_for<0, NY>([&](auto a_) { Ks[s][decltype(a_)::value] = g * F[decltype(a_)::value]; });
+      if constexpr (NG > 0) {
+        // (f stays eval_f's, so that the states round as pc_sol_propagate's do: the common subexpressions of f and g
+        // together may associate a shared sum or product differently)
+        double Fg[NY1], G[NG];
+        M::eval_fg(v, Fg, G);
+        static_for<0, NG>([&](auto m_) { Gs[s][decltype(m_)::value] = g * G[decltype(m_)::value]; });
+      }
     }
   });
+}
+
+// err = max_a |h sum_i e_i K_i,a| / (atol_a + rtol max(|y_a|, |ynew_a|)) over the N components of Ks, folded into err
+// (bad: a term is not finite)
+template <int N, int N1>
+__device__ __forceinline__ void prop_err(const double (&Ks)[7][N1], const double* y, const double* ynew, double h, const double* atol,
+                                         double rtol, double& err, bool& bad) {
+  static_for<0, N>([&](auto a_) {
+    constexpr int a = decltype(a_)::value;
+    double acc = 0.0;
+    static_for<0, 7>([&](auto i_) {
+      constexpr int i = decltype(i_)::value;
+      constexpr double w = dp_e(i);
+      if constexpr (w != 0.0) acc += w * Ks[i][a];
+    });
+    const double r = fabs(h * acc) / (atol[a] + rtol * fmax(fabs(y[a]), fabs(ynew[a])));
+    if (!(r <= 1.7976931348623157e308)) bad = true;   // NaN or inf (fmax would drop a NaN)
+    err = fmax(err, r);
+  });
+}
+
+// One step: prop_stages without integrals.  ERR: the seventh stage and err, the scaled error norm (bad: it is not
+// finite).
+template <class M, bool ERR>
+__device__ __forceinline__ void prop_step(const PcSolPropagateArgs& A, double* v, const double* y, int64_t off, int n, double c,
+                                          double h, double g, double* ynew, double& err, bool& bad) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NY1 = NY > 0 ? NY : 1;
+  double Ks[7][NY1], Gs[7][1];
+  prop_stages<M, ERR, 0>(A, v, y, nullptr, off, n, c, h, g, false, Ks, Gs, ynew, nullptr);
   if constexpr (ERR) {
     err = 0.0;
     bad = false;
-    static_for<0, NY>([&](auto a_) {
-      constexpr int a = decltype(a_)::value;
-      double acc = 0.0;
-      static_for<0, 7>([&](auto i_) {
-        constexpr int i = decltype(i_)::value;
-        constexpr double w = dp_e(i);
-        if constexpr (w != 0.0) acc += w * Ks[i][a];
-      });
-      const double r = fabs(h * acc) / (A.atol[a] + A.rtol * fmax(fabs(y[a]), fabs(ynew[a])));
-      if (!(r <= 1.7976931348623157e308)) bad = true;   // NaN or inf (fmax would drop a NaN)
-      err = fmax(err, r);
-    });
+    prop_err<NY, NY1>(Ks, y, ynew, h, A.atol, A.rtol, err, bad);
   }
 }
 
@@ -781,6 +837,176 @@ __device__ __forceinline__ void sol_propagate(const PcSolPropagateArgs& A) {
       constexpr int a = decltype(a_)::value;
       A.y_arrive[(int64_t)a * N + j + 1] = status >= 0 ? __builtin_nan("") : y[a];
     });
+  }
+  A.seg_status[i] = status;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Propagation with integrals and dense output.  pc_sol_propagate_dense_p<i>: the lane of pc_sol_propagate,
+// with the same steps, carries the phase's NQ integrals I (dI_m/dc = g g_m at the stage arguments of f, I = 0 at the
+// segment's first node) and, after every accepted step, answers the sorted queries of its node interval that the step
+// reaches: Shampine's interpolant for a query inside the step, the new state itself for a query at its end.  The
+// interval that ends at node j owns the sorted queries node_q0[j] .. node_q0[j+1] (slot 0: the queries at tau_0, answered
+// with y(0) and 0 by the lane that starts there); a query's c is formed as the nodes' is.  Answers are scattered to
+// column q_order[k]: the lane's own columns only.  Without integral_atol the integrals take no part in the error norm,
+// and the steps are pc_sol_propagate's to the bit.  No LDS, no atomics; the query cursor is bounded by Q.
+// ---------------------------------------------------------------------------------------------
+template <class M>
+__device__ __forceinline__ void sol_propagate_dense(const PcSolPropagateDenseArgs& A) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NQ = St::NQ, NY1 = NY > 0 ? NY : 1, NQ1 = NQ > 0 ? NQ : 1;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n_seg) return;
+  const int N = A.v.N;
+  const int64_t Q = A.Q;
+  const int32_t* sec_s = A.v.sec_s;
+  const int j0 = A.seg_node[i], j1 = A.seg_node[i + 1];
+  int k = A.seg_sec[i];
+  double t0, tF;
+  sol_times<M>(A.v, t0, tF);
+  const double stretch = 0.5 * (tF - t0);
+  const double nan = __builtin_nan("");
+  double v[St::NV > 0 ? St::NV : 1], y[NY1], ynew[NY1], I[NQ1], Inew[NQ1], Ks[7][NY1], Gs[7][NQ1];
+  sol_params<M>(A.v, v);
+  static_for<0, NY>([&](auto a_) {
+    constexpr int a = decltype(a_)::value;
+    y[a] = A.c.node_y[(int64_t)a * N + j0];
+    if (j0 == 0) A.y_arrive[(int64_t)a * N] = y[a];
+  });
+  static_for<0, NQ>([&](auto m_) {
+    constexpr int m = decltype(m_)::value;
+    I[m] = 0.0;
+    if (j0 == 0) A.q_arrive[(int64_t)m * N] = 0.0;
+  });
+  if (j0 == 0) {
+    A.accepted[0] = A.rejected[0] = 0;
+    for (int kq = A.node_q0[0]; kq < A.node_q0[1] && kq < Q; ++kq) {   // the queries at tau_0
+      const int64_t col = A.q_order[kq];
+      static_for<0, NY>([&](auto a_) { A.y_dense[(int64_t) decltype(a_)::value * Q + col] = y[decltype(a_)::value]; });
+      static_for<0, NQ>([&](auto m_) { A.q_dense[(int64_t) decltype(m_)::value * Q + col] = 0.0; });
+    }
+  }
+  int status = -1;
+  for (int j = j0; j < j1; ++j) {
+    int kq = A.node_q0[j + 1];
+    const int kq1 = A.node_q0[j + 2] < Q ? A.node_q0[j + 2] : (int)Q;
+    if (status < 0) {
+      if (j >= sec_s[k + 1] && k < A.v.K - 1) ++k;
+      const int sk = sec_s[k], n = sec_s[k + 1] - sk + 1;
+      const int64_t off = (int64_t)sk + k;
+      const double ta = A.c.sec_tau[k], w = A.c.sec_tau[k + 1] - ta;
+      const double ca = 2.0 * (A.tau[j] - ta) / w - 1.0, cb = 2.0 * (A.tau[j + 1] - ta) / w - 1.0;
+      const double g = stretch * (0.5 * w);
+      // the queries the step from c of width h to ce reaches (it has been accepted: ynew, Inew, Ks, Gs are its own)
+      auto answer = [&](double c, double h, double ce) {
+        while (kq < kq1) {
+          const double cq = 2.0 * (A.tau_q[kq] - ta) / w - 1.0;
+          if (!(cq <= ce)) break;
+          const int64_t col = A.q_order[kq];
+          if (cq == ce) {
+            static_for<0, NY>([&](auto a_) { A.y_dense[(int64_t) decltype(a_)::value * Q + col] = ynew[decltype(a_)::value]; });
+            static_for<0, NQ>([&](auto m_) { A.q_dense[(int64_t) decltype(m_)::value * Q + col] = Inew[decltype(m_)::value]; });
+          } else {
+            const double th = fmax((cq - c) / h, 0.0);
+            double b[7];
+            static_for<0, 7>([&](auto i_) {
+              constexpr int ii = decltype(i_)::value;
+              b[ii] = th * (dp_p(ii, 0) + th * (dp_p(ii, 1) + th * (dp_p(ii, 2) + th * dp_p(ii, 3))));
+            });
+            static_for<0, NY>([&](auto a_) {
+              constexpr int a = decltype(a_)::value;
+              double acc = 0.0;
+              static_for<0, 7>([&](auto i_) {
+                constexpr int ii = decltype(i_)::value;
+                if constexpr (dp_p_row(ii)) acc += Ks[ii][a] * b[ii];
+              });
+              A.y_dense[(int64_t)a * Q + col] = y[a] + h * acc;
+            });
+            static_for<0, NQ>([&](auto m_) {
+              constexpr int m = decltype(m_)::value;
+              double acc = 0.0;
+              static_for<0, 7>([&](auto i_) {
+                constexpr int ii = decltype(i_)::value;
+                if constexpr (dp_p_row(ii)) acc += Gs[ii][m] * b[ii];
+              });
+              A.q_dense[(int64_t)m * Q + col] = I[m] + h * acc;
+            });
+          }
+          ++kq;
+        }
+      };
+      auto advance = [&]() {
+        static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
+        static_for<0, NQ>([&](auto m_) { I[decltype(m_)::value] = Inew[decltype(m_)::value]; });
+      };
+      int n_acc = 0, n_rej = 0;
+      if (A.substeps > 0) {
+        const int m = A.substeps;
+        const double h = (cb - ca) / (double)m;
+        for (int q = 0; q < m; ++q) {
+          const double c = ca + (double)q * h;
+          const double hq = q == m - 1 ? cb - c : h, ce = q == m - 1 ? cb : c + h;
+          // the seventh stage only where a query falls into the step
+          const bool hit = kq < kq1 && 2.0 * (A.tau_q[kq] - ta) / w - 1.0 <= ce;
+          prop_stages<M, false, NQ>(A, v, y, I, off, n, c, hq, g, hit, Ks, Gs, ynew, Inew);
+          if (hit) answer(c, hq, ce);
+          advance();
+        }
+        n_acc = m;
+      } else {
+        double c = ca, h = cb - ca;
+        bool last = true, after_reject = false, done = false;
+        while (!done && n_acc + n_rej < A.max_steps) {
+          prop_stages<M, true, NQ>(A, v, y, I, off, n, c, h, g, true, Ks, Gs, ynew, Inew);
+          double err = 0.0;
+          bool bad = false;
+          prop_err<NY, NY1>(Ks, y, ynew, h, A.atol, A.rtol, err, bad);
+          if (A.integral_atol) prop_err<NQ, NQ1>(Gs, I, Inew, h, A.integral_atol, A.rtol, err, bad);
+          double factor = 0.2;
+          if (!bad) factor = err == 0.0 ? 5.0 : fmin(5.0, fmax(0.2, 0.9 * pow(err, -0.2)));
+          if (!bad && err <= 1.0) {
+            ++n_acc;
+            const double ce = last ? cb : c + h;
+            answer(c, h, ce);
+            advance();
+            c = ce;
+            if (after_reject) factor = fmin(factor, 1.0);
+            after_reject = false;
+            const double rest = cb - c;
+            if (last || !(rest > 0.0)) {
+              done = true;
+            } else {
+              h *= factor;
+              last = h >= rest;
+              if (last) h = rest;
+            }
+          } else {
+            ++n_rej;
+            h *= factor;
+            last = false;
+            after_reject = true;
+          }
+        }
+        if (!done) status = j;
+      }
+      A.accepted[j + 1] = n_acc;
+      A.rejected[j + 1] = n_rej;
+    } else {   // behind the interval that failed
+      A.accepted[j + 1] = A.rejected[j + 1] = 0;
+    }
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      A.y_arrive[(int64_t)a * N + j + 1] = status >= 0 ? nan : y[a];
+    });
+    static_for<0, NQ>([&](auto m_) {
+      constexpr int m = decltype(m_)::value;
+      A.q_arrive[(int64_t)m * N + j + 1] = status >= 0 ? nan : I[m];
+    });
+    for (; kq < kq1; ++kq) {   // the queries no accepted step has reached: behind the failure
+      const int64_t col = A.q_order[kq];
+      static_for<0, NY>([&](auto a_) { A.y_dense[(int64_t) decltype(a_)::value * Q + col] = nan; });
+      static_for<0, NQ>([&](auto m_) { A.q_dense[(int64_t) decltype(m_)::value * Q + col] = nan; });
+    }
   }
   A.seg_status[i] = status;
 }
@@ -915,6 +1141,9 @@ __device__ __forceinline__ void mesh_error(const PcRefineArgs& A) {
   }                                                                                                          \
   extern "C" __global__ void __launch_bounds__(PC_SOL_PROP_TB) pc_sol_propagate_p##I(PcSolPropagateArgs a) { \
     pc::sol_propagate<gen::Phase##I>(a);                                                                     \
+  }                                                                                                          \
+  extern "C" __global__ void __launch_bounds__(PC_SOL_PROP_TB) pc_sol_propagate_dense_p##I(PcSolPropagateDenseArgs a) { \
+    pc::sol_propagate_dense<gen::Phase##I>(a);                                                               \
   }                                                                                                          \
   extern "C" __global__ void __launch_bounds__(256) pc_sol_multipliers_p##I(PcSolMultiplierArgs a) {         \
     pc::sol_multipliers<gen::Phase##I>(a);                                                                   \

@@ -13,6 +13,7 @@
 //
 // Propagation (pc_solution_propagate): the index arithmetic is pc_propagate_plan.hpp.  The segment list, the first
 // sections and atol are staged in buffers the solution keeps, so a device call may return before the kernel has run.
+// pc_solution_propagate_dense stages its own lists the same way, and with them integral_atol and the sorted queries.
 //
 // Path and bound multipliers (pc_solution_set_bound_multipliers): the index arithmetic is pc_optimality_plan.hpp.  The
 // solution keeps its own device copy of the constraint multipliers, the tables and the scaling they were set under, so
@@ -43,7 +44,10 @@ struct pc_solution {
     PcPhaseView view_w;     // view with the constraint scaling the multipliers were set under
     DevBuf<int32_t> prop_seg, prop_sec;          // propagation: the staged segment list and first sections,
     DevBuf<double> prop_atol;                    // and atol
-    hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr, fn_propagate = nullptr;
+    DevBuf<int32_t> dense_seg, dense_sec, dense_order, dense_q0;   // dense propagation: its own staged lists,
+    DevBuf<double> dense_atol, dense_iatol, dense_tau_q;           // tolerances and sorted queries
+    std::vector<double> h_tau;                   // the node abscissae on the host (the queries' slots are found in them)
+    hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr, fn_propagate = nullptr, fn_propagate_dense = nullptr;
     PcPhaseView view;       // the phase as of creation: what sampling, the costates and propagation unscale with
     PcSolCurves curves;     // the polynomials the fit kernel made
     int NY = 0, NU = 0, NQ = 0;
@@ -78,7 +82,8 @@ void solution_build(pc_solution* s, int n_orders, const int32_t* orders, const d
     const std::vector<double> edges = pcs::section_edges(F, tau + tau_off);
     S->tile_k0.upload(F.tile_k0);
     S->lane0.upload(F.lane0);
-    S->node_tau.upload(std::vector<double>(tau + tau_off, tau + tau_off + P.N));
+    S->h_tau.assign(tau + tau_off, tau + tau_off + P.N);
+    S->node_tau.upload(S->h_tau);
     tau_off += (size_t)P.N;
     S->sec_tau.upload(edges);
     const size_t ny = (size_t)std::max(1, P.n_y), nu = (size_t)std::max(1, P.n_u);
@@ -387,6 +392,57 @@ void solution_launch_propagate(pc_solution* s, int phase, int64_t n_seg, const i
   launch_block(S.fn_propagate, (unsigned)P.blocks, (unsigned)P.TB, 0, s->h->stream, a);
 }
 
+// pc_sol_propagate_dense_p<phase> on the handle's stream; the outputs are device arrays ([n_y][N], [N], [N], [n_seg],
+// [n_q][N], [n_y][n_query], [n_q][n_query]); the queries are tau, a host array
+void solution_launch_propagate_dense(pc_solution* s, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps,
+                                     double rtol, const double* atol, const double* integral_atol, int64_t max_steps,
+                                     int64_t n_query, const double* tau_q, double* d_y, int32_t* d_acc, int32_t* d_rej,
+                                     int32_t* d_status, double* d_q, double* d_yd, double* d_qd) {
+  auto& S = *s->ph[phase];
+  pcs::check_propagate_tolerances(substeps, rtol, atol, S.NY, max_steps);
+  pcs::check_integral_atol(integral_atol, S.NQ);
+  const pcs::PropagatePlan P = pcs::build_propagate_plan(S.plan, n_seg, seg_nodes);
+  const pcs::DenseQueryPlan D = pcs::build_dense_query_plan(S.plan.N, S.h_tau.data(), n_query, tau_q);
+  if (!d_acc || !d_rej || !d_status || (S.NY > 0 && !d_y) || (S.NQ > 0 && !d_q) ||
+      (D.Q > 0 && ((S.NY > 0 && !d_yd) || (S.NQ > 0 && !d_qd))))
+    throw std::runtime_error("propagate: null output");
+  if (!S.fn_propagate_dense)
+    HIP_OK(find_fn(s->h, &S.fn_propagate_dense, ("pc_sol_propagate_dense_p" + std::to_string(phase)).c_str()));
+  HIP_OK(hipStreamSynchronize(s->h->stream));   // an earlier call may still read the staged lists
+  S.dense_seg.upload(P.seg_node);
+  S.dense_sec.upload(P.seg_sec);
+  S.dense_atol.upload(std::vector<double>(atol, atol + S.NY));
+  if (integral_atol) S.dense_iatol.upload(std::vector<double>(integral_atol, integral_atol + S.NQ));
+  S.dense_tau_q.upload(D.tau_sorted);
+  S.dense_order.upload(D.q_order);
+  S.dense_q0.upload(D.node_q0);
+  PcSolPropagateDenseArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.v = S.view;
+  a.c = S.curves;
+  a.tau = S.node_tau.p;
+  a.seg_node = S.dense_seg.p;
+  a.seg_sec = S.dense_sec.p;
+  a.atol = S.dense_atol.p;
+  a.integral_atol = integral_atol && S.NQ > 0 ? S.dense_iatol.p : nullptr;
+  a.tau_q = S.dense_tau_q.p;
+  a.q_order = S.dense_order.p;
+  a.node_q0 = S.dense_q0.p;
+  a.y_arrive = d_y;
+  a.accepted = d_acc;
+  a.rejected = d_rej;
+  a.seg_status = d_status;
+  a.q_arrive = d_q;
+  a.y_dense = d_yd;
+  a.q_dense = d_qd;
+  a.rtol = rtol;
+  a.Q = D.Q;
+  a.n_seg = P.n_seg;
+  a.substeps = (int32_t)substeps;
+  a.max_steps = (int32_t)max_steps;
+  launch_block(S.fn_propagate_dense, (unsigned)P.blocks, (unsigned)P.TB, 0, s->h->stream, a);
+}
+
 pc_solution::Phase& solution_costate_phase(pc_solution* s, int phase) {
   auto& S = solution_phase(s, phase);
   if (!s->has_costate) throw std::runtime_error("solution: no multipliers were set");
@@ -654,6 +710,52 @@ int pc_solution_propagate_device(pc_solution* sol, int phase, int64_t n_seg, con
     (void)solution_phase(sol, phase);
     solution_launch_propagate(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, d_y_arrive, d_accepted, d_rejected,
                               d_seg_status);
+  });
+}
+
+int pc_solution_propagate_dense(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
+                                const double* atol, const double* integral_atol, int64_t max_steps, int64_t n_query,
+                                const double* tau_q, double* y_arrive, int32_t* accepted, int32_t* rejected, int32_t* seg_status,
+                                double* q_arrive, double* y_dense, double* q_dense) {
+  return guarded(g_err, [&] {
+    auto& S = solution_phase(sol, phase);
+    if (!accepted || !rejected || !seg_status || (S.NY > 0 && !y_arrive) || (S.NQ > 0 && !q_arrive) ||
+        (n_query > 0 && ((S.NY > 0 && !y_dense) || (S.NQ > 0 && !q_dense))))
+      throw std::runtime_error("propagate: null output");
+    if (n_seg < 1 || n_seg > (int64_t)S.plan.N - 1) throw std::runtime_error("propagate: the number of segments must be in [1, N - 1]");
+    if (n_query < 0 || n_query > (int64_t)INT32_MAX) throw std::runtime_error("propagate: the number of queries must be in [0, 2^31)");
+    const size_t N = (size_t)S.plan.N, Qn = (size_t)n_query;
+    DevBuf<double> d_y, d_q, d_yd, d_qd;
+    DevBuf<int32_t> d_acc, d_rej, d_st;
+    d_y.alloc(N * (size_t)std::max(1, S.NY));
+    d_q.alloc(N * (size_t)std::max(1, S.NQ));
+    d_yd.alloc(Qn * (size_t)S.NY);
+    d_qd.alloc(Qn * (size_t)S.NQ);
+    d_acc.alloc(N);
+    d_rej.alloc(N);
+    d_st.alloc((size_t)n_seg);
+    solution_launch_propagate_dense(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, integral_atol, max_steps, n_query, tau_q,
+                                    d_y.p, d_acc.p, d_rej.p, d_st.p, d_q.p, d_yd.p, d_qd.p);
+    HIP_OK(hipStreamSynchronize(sol->h->stream));
+    solution_down(y_arrive, d_y, N * S.NY);
+    solution_down(q_arrive, d_q, N * S.NQ);
+    solution_down(y_dense, d_yd, Qn * S.NY);
+    solution_down(q_dense, d_qd, Qn * S.NQ);
+    HIP_OK(hipMemcpy(accepted, d_acc.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(rejected, d_rej.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(seg_status, d_st.p, (size_t)n_seg * sizeof(int32_t), hipMemcpyDeviceToHost));
+  });
+}
+
+int pc_solution_propagate_dense_device(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps,
+                                       double rtol, const double* atol, const double* integral_atol, int64_t max_steps,
+                                       int64_t n_query, const double* tau_q, double* d_y_arrive, int32_t* d_accepted,
+                                       int32_t* d_rejected, int32_t* d_seg_status, double* d_q_arrive, double* d_y_dense,
+                                       double* d_q_dense) {
+  return guarded(g_err, [&] {
+    (void)solution_phase(sol, phase);
+    solution_launch_propagate_dense(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, integral_atol, max_steps, n_query, tau_q,
+                                    d_y_arrive, d_accepted, d_rejected, d_seg_status, d_q_arrive, d_y_dense, d_q_dense);
   });
 }
 

@@ -68,7 +68,10 @@ multipliers of the scaled NLP's ``num_x`` variables:
 Propagation (:meth:`Solution.propagate`; no reference counterpart): the dynamics integrated forward under the
 solution's control interpolant by the Dormand-Prince 5(4) pair, restarted from the NLP's own state at chosen nodes
 (``pc_sol_propagate_p<i>``, one lane per restart).  ``defect = y_arrive - state`` is what the collocation residual
-accumulates to over a node interval, a section or the whole phase.
+accumulates to over a node interval, a section or the whole phase.  :meth:`Solution.propagate_dense` (DESIGN 8g;
+``pc_sol_propagate_dense_p<i>``) takes the same steps, carries the phase's integrals beside the state
+(``integral_defect`` = what they come to, less the NLP's integral variables) and samples the propagated path between the
+nodes by the pair's continuous extension.
 """
 from __future__ import annotations
 
@@ -162,6 +165,78 @@ class Propagation:
     status: object
     ok: object
     terminal_defect: object
+
+
+@dataclasses.dataclass
+class DensePropagation:
+    """What :meth:`Solution.propagate_dense` returns (NumPy arrays, or torch tensors on the device of the call's inputs).
+    ``y``, ``defect``, ``relative_defect``, ``terminal_defect``, ``accepted``, ``rejected``, ``segments``, ``status``,
+    ``ok``: as in :class:`Propagation`.  ``q`` [n_q][N]: column j >= 1 is the integral of the integrands from the first
+    node of the segment that contains the interval (j - 1, j) to node j, column 0 is 0.  ``integral`` [n_q]: the sum of
+    ``q`` over the segments' last nodes, the whole phase's integrals; ``integral_defect`` = ``integral`` - the NLP's
+    (unscaled) integral variables.  ``tau`` [Q]: the queries as abscissae; ``y_dense`` [n_y][Q], ``q_dense`` [n_q][Q]
+    (the integral from the first node of the query's segment) and ``u_dense`` [n_u][Q] (the control interpolant,
+    :meth:`Solution.sample`'s) in the caller's query order."""
+    y: object
+    defect: object
+    relative_defect: object
+    accepted: object
+    rejected: object
+    segments: np.ndarray
+    status: object
+    ok: object
+    terminal_defect: object
+    q: object
+    integral: object
+    integral_defect: object
+    tau: np.ndarray
+    y_dense: object
+    q_dense: object
+    u_dense: object
+
+
+def dense_query_tau(t, tau, t0: float, tF: float) -> np.ndarray:
+    """The queries of ``Solution.propagate_dense`` as abscissae: ``tau`` itself, or ``t`` mapped as the sampling kernel
+    maps it (a time within 8 eps in tau of the phase's ends is the end).  ``ValueError`` for a NaN and for a query
+    outside the phase; both ``None``: no queries."""
+    if t is None and tau is None:
+        return np.zeros(0)
+    q, is_tau = normalise_query(t, tau)
+    if _is_torch(q):
+        q = q.detach().cpu().numpy()
+    q = np.ascontiguousarray(q, dtype=np.float64)
+    if np.isnan(q).any():
+        raise ValueError("a query is NaN")
+    if not is_tau:
+        q = (q - 0.5 * (t0 + tF)) / (0.5 * (tF - t0))
+        near = np.abs(q) <= 1.0 + END_SLACK
+        q = np.where(near, np.clip(q, -1.0, 1.0), q)
+    if q.size and not (q.min() >= -1.0 and q.max() <= 1.0):
+        raise ValueError(f"queries reach tau = [{float(q.min())!r}, {float(q.max())!r}], outside the phase's [-1, 1]: a "
+                         f"propagated path is not extrapolated")
+    return np.ascontiguousarray(q)
+
+
+def _sum_ascending(cols: np.ndarray) -> np.ndarray:
+    """sum over the columns, first to last, one addition per column (``np.sum`` adds pairwise)"""
+    cols = np.asarray(cols, dtype=np.float64)
+    return np.cumsum(cols, axis=1)[:, -1] if cols.shape[1] else np.zeros(cols.shape[0])
+
+
+def check_integral_atol(integral_atol, n_q: int):
+    """``None``, or ``n_q`` finite positive numbers as a contiguous float64 array (csrc/pc_propagate_plan.hpp makes the
+    same refusal)."""
+    if integral_atol is None:
+        return None
+    if _is_torch(integral_atol):
+        integral_atol = integral_atol.detach().cpu().numpy()
+    try:
+        ia = np.ascontiguousarray(np.broadcast_to(np.asarray(integral_atol, dtype=np.float64), (n_q,)))
+    except ValueError:
+        raise ValueError(f"integral_atol must be a number or {n_q} numbers") from None
+    if not (np.all(np.isfinite(ia)) and np.all(ia > 0)):
+        raise ValueError("every integral_atol must be finite and positive")
+    return ia
 
 
 def propagation_segments(restart, s, N: int) -> np.ndarray:
@@ -416,6 +491,9 @@ class Solution:
         prop = [vp, C.c_int, C.c_int64, vp, C.c_int64, C.c_double, vp, C.c_int64, vp, vp, vp, vp]
         lib.pc_solution_propagate.argtypes = prop
         lib.pc_solution_propagate_device.argtypes = prop
+        dense = [vp, C.c_int, C.c_int64, vp, C.c_int64, C.c_double, vp, vp, C.c_int64, C.c_int64, vp] + [vp] * 7
+        lib.pc_solution_propagate_dense.argtypes = dense
+        lib.pc_solution_propagate_dense_device.argtypes = dense
         lib.pc_solution_set_bound_multipliers.argtypes = [vp, vp, C.c_int64]
         lib.pc_solution_set_bound_multipliers_device.argtypes = [vp, vp, C.c_int64]
         lib.pc_solution_multiplier_nodes.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
@@ -858,3 +936,78 @@ class Solution:
         defect = y - node_y
         return Propagation(y=y, defect=defect, relative_defect=defect / scale, accepted=acc, rejected=rej, segments=seg,
                            status=status, ok=status == -1, terminal_defect=defect[:, -1])
+
+    def propagate_dense(self, phase: int, t=None, *, tau=None, restart="nodes", rtol: float = 1e-9, atol=None,
+                        integral_atol=None, substeps=None, max_steps: int = 4096):
+        """:meth:`propagate` with the phase's integrals carried along and the propagated path sampled between the nodes
+        (``pc_sol_propagate_dense_p<i>``); returns a :class:`DensePropagation`.
+
+        ``restart``, ``rtol``, ``atol``, ``substeps``, ``max_steps``: as in :meth:`propagate`, and the steps are the
+        same.  The integrals I_m follow dI_m/dc = stretch (w_k / 2) g_m from 0 at every segment's first node.
+        ``integral_atol=None``: they take no part in the step control, and ``y``, ``accepted``, ``rejected`` and
+        ``status`` equal :meth:`propagate`'s to the bit.  ``integral_atol`` (a number or n_q numbers, finite and
+        positive): integral m adds |e_m| / (integral_atol_m + rtol max(|I_m|, |I_m,new|)) to the adaptive error norm.
+
+        ``t`` (times) or ``tau`` (abscissae in [-1, 1]), any order, duplicates allowed, or neither (the integrals
+        only): where the path is wanted.  A query belongs to the node interval (tau_j, tau_j+1] that holds it and is
+        answered by the first accepted step that reaches it, through the pair's continuous extension (fourth order);
+        at a node it is the arriving value itself.  Queries behind an interval that used up ``max_steps`` are NaN.
+        A NaN query or one outside the phase raises ``ValueError``: there is no extrapolation of a propagated path.
+
+        NumPy out, unless ``t`` / ``tau``, ``restart``, ``atol`` or ``integral_atol`` is a torch device tensor: then
+        torch tensors on that device.  Bad arguments raise ``ValueError`` before anything is launched."""
+        phase = self._phase(phase, need_handle=False)
+        pl, mesh = self.engine.layout.phases[phase], self.engine.meshes[phase]
+        N, n_y, n_q = pl.N, pl.n_y, pl.n_q
+        device = next((a.device for a in (t, tau, restart, atol, integral_atol) if _is_torch(a) and a.is_cuda), None)
+        seg = propagation_segments(restart, mesh.s, N)
+        V = self.state_scale(phase)
+        if atol is None:
+            at = float(rtol) * V
+        else:
+            if _is_torch(atol):
+                atol = atol.detach().cpu().numpy()
+            at = np.ascontiguousarray(np.broadcast_to(np.asarray(atol, dtype=np.float64), (n_y,)))
+        check_propagate_tolerances(substeps, rtol, at, max_steps)
+        at = np.ascontiguousarray(at, dtype=np.float64)
+        ia = check_integral_atol(integral_atol, n_q)
+        tq = dense_query_tau(t, tau, self.initial_time[phase], self.final_time[phase])
+        self._phase(phase)     # (the device is needed from here on)
+        Q, n_seg, m = int(tq.shape[0]), len(seg) - 1, 0 if substeps is None else int(substeps)
+        head = (self._h, phase, n_seg, seg.ctypes.data, m, float(rtol), at.ctypes.data if n_y else None,
+                ia.ctypes.data if (ia is not None and n_q) else None, int(max_steps), Q, tq.ctypes.data if Q else None)
+        q_nlp = np.asarray(self.integral[phase], dtype=np.float64).reshape(n_q)
+        ends = seg[1:].astype(np.int64)
+        if device is not None:
+            import torch
+            new = lambda sh, dt=torch.float64: torch.empty(sh, dtype=dt, device=device)   # noqa: E731
+            y, qa, yd, qd = new((n_y, N)), new((n_q, N)), new((n_y, Q)), new((n_q, Q))
+            acc, rej, status = new((N,), torch.int32), new((N,), torch.int32), new((n_seg,), torch.int32)
+            ptr = lambda a: a.data_ptr() if a.numel() else None   # noqa: E731
+            torch.cuda.current_stream(device).synchronize()     # the handle's stream is not torch's
+            self._check(self._lib.pc_solution_propagate_dense_device(*head, ptr(y), ptr(acc), ptr(rej), ptr(status), ptr(qa),
+                                                                     ptr(yd), ptr(qd)))
+            self._check(self._lib.pc_synchronize(self.engine._h))
+            node_y = torch.as_tensor(np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N), device=device)
+            scale = torch.as_tensor(V, device=device)[:, None]
+            integral = torch.as_tensor(_sum_ascending(qa[:, torch.as_tensor(ends, device=device)].cpu().numpy()), device=device)
+            q_nlp = torch.as_tensor(q_nlp, device=device)
+            tq_where = torch.as_tensor(tq, device=device)
+        else:
+            y, qa, yd, qd = np.empty((n_y, N)), np.empty((n_q, N)), np.empty((n_y, Q)), np.empty((n_q, Q))
+            acc, rej, status = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32), np.empty(n_seg, dtype=np.int32)
+            ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
+            self._check(self._lib.pc_solution_propagate_dense(*head, ptr(y), ptr(acc), ptr(rej), ptr(status), ptr(qa), ptr(yd),
+                                                              ptr(qd)))
+            node_y = np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N)
+            scale = V[:, None]
+            integral = _sum_ascending(qa[:, ends])
+            tq_where = tq
+        if Q:
+            u_dense = self.sample(phase, tau=tq_where)[2]
+        else:
+            u_dense = yd.new_empty((pl.n_u, 0)) if device is not None else np.empty((pl.n_u, 0))
+        defect = y - node_y
+        return DensePropagation(y=y, defect=defect, relative_defect=defect / scale, accepted=acc, rejected=rej, segments=seg,
+                                status=status, ok=status == -1, terminal_defect=defect[:, -1], q=qa, integral=integral,
+                                integral_defect=integral - q_nlp, tau=tq, y_dense=yd, q_dense=qd, u_dense=u_dense)
