@@ -658,6 +658,31 @@ int pc_solution_propagate_device(pc_solution* sol, int phase, int64_t n_seg, con
                                  const double* atol, int64_t max_steps, double* d_y_arrive, int32_t* d_accepted,
                                  int32_t* d_rejected, int32_t* d_seg_status);
 
+/* ---- forward propagation by an implicit method, for stiff phases (no reference counterpart) ----
+ * pc_solution_propagate's segments, intervals and outputs, integrated by the five-stage L-stable SDIRK method of order 4
+ * of Hairer & Wanner (gamma = 1/4, embedded weights of order 3).  One attempt of width h: J = g df/dy at the step's start,
+ * W = I - h gamma J factored once by LU with partial pivoting; per stage a Newton iteration on the stage derivative K,
+ * at most newton_max (1 .. 32) times, ended when theta = max_a |h gamma dK_a| / (atol_a + rtol max(|y_a|, |Y_a|)) <= 0.01;
+ * a theta that is not finite, newton_max used up or an unusable pivot is a Newton failure.  The error estimate is
+ * filtered through W^-1.
+ *   substeps = m >= 1: m equal steps per node interval; rtol is still read (the Newton iteration stops by it) and must be
+ *     finite and positive in both modes.  A Newton failure ends the segment at that interval as the cap does.
+ *   substeps = 0: adaptive, as pc_solution_propagate with factor = clamp(0.9 err^(-1/4), 0.2, 5); a Newton failure
+ *     rejects the step with factor 0.25.
+ * Further outputs: newton_rejected [N] (the rejected steps of the interval whose cause was a Newton failure; they count
+ * in rejected too) and newton_iterations [N] (all Newton iterations of the interval); column 0: 0.  A phase with more than
+ * 11 states (PC_SOL_STIFF_MAX_NY: a lane's factors live in LDS) is refused.  Runs pc_sol_propagate_stiff_p<i> on the
+ * handle's stream.  Host pointers for the outputs; synchronises. */
+int pc_solution_propagate_stiff(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
+                                const double* atol, int64_t max_steps, int64_t newton_max, double* y_arrive, int32_t* accepted,
+                                int32_t* rejected, int32_t* seg_status, int32_t* newton_rejected, int32_t* newton_iterations);
+/* the same with device pointers for the six outputs (seg_nodes and atol stay host arrays); queued on the handle's
+ * stream, does not synchronise behind the launch */
+int pc_solution_propagate_stiff_device(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps,
+                                       double rtol, const double* atol, int64_t max_steps, int64_t newton_max, double* d_y_arrive,
+                                       int32_t* d_accepted, int32_t* d_rejected, int32_t* d_seg_status,
+                                       int32_t* d_newton_rejected, int32_t* d_newton_iterations);
+
 /* ---- propagation with integrals and dense output (no reference counterpart) ----
  * pc_solution_propagate's segments, steps and step control, and beside the state the phase's n_q integrals I_m with
  * dI_m/dc = stretch (w_k / 2) g_m(y, u(c), q, t0, tF, s), I = 0 at every segment's first node, by the same tableau.

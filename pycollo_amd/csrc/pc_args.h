@@ -524,4 +524,28 @@ struct PcSolPropagateDenseArgs {
   int32_t n_seg, substeps, max_steps, reserved;
 };
 
+// Arguments of the implicit propagation (pc_solution.hpp, pc_sol_propagate_stiff): the segments, tolerances
+// and outputs of PcSolPropagateArgs, integrated by the L-stable SDIRK method of order 4 with a Newton iteration per
+// stage.  A lane keeps the LU factors of its NY x NY iteration matrix and their row swaps in LDS, element e of lane l at
+// [e * PC_SOL_PROP_TB + l]: NY^2 doubles and NY int32 per lane, which is what bounds NY.
+#define PC_SOL_STIFF_MAX_NY 11         // 11^2 * 512 B of factors + 11 * 256 B of row swaps = 64 768 B <= 64 KiB of static LDS
+#define PC_SOL_STIFF_MAX_NEWTON 32     // largest newton_max
+struct PcSolPropagateStiffArgs {
+  PcPhaseView v;
+  PcSolCurves c;
+  const double* tau;           // [N]
+  const int32_t* seg_node;     // [n_seg+1]
+  const int32_t* seg_sec;      // [n_seg]
+  const double* atol;          // [NY]
+  double* y_arrive;            // [NY][N] as in PcSolPropagateArgs, like the next three
+  int32_t* accepted;           // [N]
+  int32_t* rejected;           // [N] error rejections and Newton failures
+  int32_t* seg_status;         // [n_seg] -1: complete, else the first node of the interval that used up max_steps or,
+                               //   in fixed mode, whose Newton iteration failed
+  int32_t* newton_rejected;    // [N] the rejected steps of the interval whose cause was a Newton failure (column 0: 0)
+  int32_t* newton_iterations;  // [N] all Newton iterations of the interval, those of rejected steps included
+  double rtol;
+  int32_t n_seg, substeps, max_steps, newton_max;   // substeps 0: adaptive
+};
+
 #endif  // PC_ARGS_H

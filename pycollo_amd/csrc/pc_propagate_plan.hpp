@@ -2,7 +2,9 @@
 // tests/c/propagate_plan_sanitize.cpp runs it under AddressSanitizer + UBSan).  The checks of the segment list and of
 // the tolerances, the first section of every segment and the grid.  The sections are the fit kernel's
 // (pc_solution_plan.hpp).  For pc_sol_propagate_dense also the check of integral_atol and the queries: their
-// checks, their stable sort and the slot of every query (tests/c/propagate_dense_plan_sanitize.cpp).
+// checks, their stable sort and the slot of every query (tests/c/propagate_dense_plan_sanitize.cpp).  For
+// pc_sol_propagate_stiff the check of its options and the lane's LDS indexing
+// (tests/c/propagate_stiff_plan_sanitize.cpp).
 #ifndef PC_PROPAGATE_PLAN_HPP
 #define PC_PROPAGATE_PLAN_HPP
 
@@ -10,6 +12,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <string>
 
 #include "pc_solution_plan.hpp"
 
@@ -32,6 +35,29 @@ inline void check_propagate_tolerances(int64_t substeps, double rtol, const doub
   for (int a = 0; a < NY; ++a)
     if (!(std::isfinite(atol[a]) && atol[a] > 0.0)) throw std::runtime_error("propagate: every atol must be finite and positive");
   if (max_steps < 1 || max_steps > PC_SOL_PROP_MAX_STEPS) throw std::runtime_error("propagate: max_steps outside [1, 2^20]");
+}
+
+// The options of the implicit method (pc_sol_propagate_stiff): the checks above, except that rtol counts in
+// both modes (the Newton iteration stops by it), and newton_max in 1 .. PC_SOL_STIFF_MAX_NEWTON.  NY above
+// PC_SOL_STIFF_MAX_NY is refused: the lane's factors would not fit a workgroup's LDS.
+inline void check_propagate_stiff_options(int64_t substeps, double rtol, const double* atol, int NY, int64_t max_steps,
+                                          int64_t newton_max) {
+  if (NY > PC_SOL_STIFF_MAX_NY)
+    throw std::runtime_error("propagate: the implicit method takes phases of at most " + std::to_string(PC_SOL_STIFF_MAX_NY) +
+                             " states (PC_SOL_STIFF_MAX_NY), this one has " + std::to_string(NY));
+  if (!(std::isfinite(rtol) && rtol > 0.0)) throw std::runtime_error("propagate: rtol must be finite and positive");
+  check_propagate_tolerances(substeps, rtol, atol, NY, max_steps);
+  if (newton_max < 1 || newton_max > PC_SOL_STIFF_MAX_NEWTON)
+    throw std::runtime_error("propagate: newton_max outside [1, " + std::to_string(PC_SOL_STIFF_MAX_NEWTON) + "]");
+}
+
+// Where element e (row-major in the NY x NY block, e < NY^2) of lane l's factors and row swap k (k < NY) lie in the
+// workgroup's two LDS arrays of pc_sol_propagate_stiff: the kernel's own expressions, restated for the host tests.
+inline int64_t stiff_lu_index(int e, int lane, int TB = PC_SOL_PROP_TB) { return (int64_t)e * TB + lane; }
+inline int64_t stiff_piv_index(int k, int lane, int TB = PC_SOL_PROP_TB) { return (int64_t)k * TB + lane; }
+inline int64_t stiff_lds_bytes(int NY, int TB = PC_SOL_PROP_TB) {
+  const int64_t n = NY > 0 ? NY : 1;
+  return n * n * TB * (int64_t)sizeof(double) + n * TB * (int64_t)sizeof(int32_t);
 }
 
 inline PropagatePlan build_propagate_plan(const FitPlan& F, int64_t n_seg, const int32_t* seg_nodes, int TB = PC_SOL_PROP_TB) {

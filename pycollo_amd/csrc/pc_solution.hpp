@@ -1122,6 +1122,316 @@ __device__ __forceinline__ void mesh_error(const PcRefineArgs& A) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Implicit propagation: the setting of pc_sol_propagate (segments, node intervals, the section variable c,
+// dy/dc = g f(y, u(c), ...), g = stretch w_k / 2, no step astride a node), integrated by the five-stage SDIRK method of
+// Hairer & Wanner (Solving ODEs II, IV.6): order 4, gamma = 1/4, stiffly accurate, L-stable, embedded weights of order 3.
+//
+// pc_sol_propagate_stiff_p<i>: one lane per segment, one wave per workgroup.  One attempt of width h from (c, y):
+//   J = g df/dy from one M::eval_fj at (y, u(c)) (the entries with row and column below NY); W = I - h gamma J factored
+//   by LU with partial pivoting (largest |entry| of the column, the lowest row on ties), once, for the five stages and
+//   the error filter; a pivot that is zero or not finite is a Newton failure.
+//   Stage i: u_i = u(c + c_i h) once; K starts as K_{i-1} (g f(y, u(c)) for stage 1); up to newton_max times
+//     Y = y + h (sum_{l<i} a_il K_l + gamma K),  r = g f(Y, u_i) - K,  dK = W^-1 r,  K += dK,
+//     theta = max_a |h gamma dK_a| / (atol_a + rtol max(|y_a|, |Y_a|));  theta <= 0.01 ends the stage; a theta that is
+//     not finite, or newton_max used up, is a Newton failure.
+//   ynew = y + h sum_i b_i K_i;  e = W^-1 (h sum_i (b_i - b^_i) K_i);  err = max_a |e_a| / (atol_a + rtol max(|y_a|, |ynew_a|)).
+//   adaptive (substeps = 0): as pc_sol_propagate with factor = clamp(0.9 err^(-1/4), 0.2, 5); a Newton failure rejects
+//     with factor 0.25 and counts in rejected and in newton_rejected.
+//   fixed (substeps = m): m steps as pc_sol_propagate places them; a Newton failure ends the lane at that interval as
+//     the cap does (the failed attempt is the interval's one rejected step).
+// The five stage vectors and y live in registers, fully unrolled.  The factors and the row swaps live in LDS, element e
+// of the lane's column at [e * PC_SOL_PROP_TB + lane]: lanes that read the same element read consecutive words, no lane
+// reads another lane's column, so there is no barrier and no atomic.  Every loop is bounded by max_steps, substeps,
+// newton_max, NY or N.  A phase with NY > PC_SOL_STIFF_MAX_NY gets an empty kernel; the host call refuses it.
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ constexpr double sd_a(int s, int i) {
+  constexpr double t[5][5] = {{1.0 / 4.0, 0.0, 0.0, 0.0, 0.0},
+                              {1.0 / 2.0, 1.0 / 4.0, 0.0, 0.0, 0.0},
+                              {17.0 / 50.0, -1.0 / 25.0, 1.0 / 4.0, 0.0, 0.0},
+                              {371.0 / 1360.0, -137.0 / 2720.0, 15.0 / 544.0, 1.0 / 4.0, 0.0},
+                              {25.0 / 24.0, -49.0 / 48.0, 125.0 / 16.0, -85.0 / 12.0, 1.0 / 4.0}};   // row 5 = b
+  return t[s][i];
+}
+__host__ __device__ constexpr double sd_c(int s) {
+  constexpr double t[5] = {1.0 / 4.0, 3.0 / 4.0, 11.0 / 20.0, 1.0 / 2.0, 1.0};
+  return t[s];
+}
+__host__ __device__ constexpr double sd_e(int s) {   // b - b^
+  constexpr double t[5] = {-3.0 / 16.0, -27.0 / 32.0, 25.0 / 32.0, 0.0, 1.0 / 4.0};
+  return t[s];
+}
+constexpr double SD_GAMMA = 1.0 / 4.0;
+constexpr double SD_NEWTON_TOL = 0.01;
+
+// the lane's column of LDS: element (r, c) of its NY x NY block, and row swap k
+#define PC_SD_LU(r, c) lu[((r) * NY + (c)) * PC_SOL_PROP_TB + lane]
+#define PC_SD_PIV(k) piv[(k) * PC_SOL_PROP_TB + lane]
+
+// LU with partial pivoting in place: rows swapped whole, unit lower factor below the diagonal.  false: a pivot is zero
+// or not finite.
+template <int NY>
+__device__ __forceinline__ bool stiff_factor(double* lu, int32_t* piv, int lane) {
+#pragma unroll 1
+  for (int k = 0; k < NY; ++k) {
+    int p = k;
+    double best = fabs(PC_SD_LU(k, k));
+    for (int r = k + 1; r < NY; ++r) {
+      const double m = fabs(PC_SD_LU(r, k));
+      if (m > best) {
+        best = m;
+        p = r;
+      }
+    }
+    PC_SD_PIV(k) = p;
+    if (p != k)
+      for (int c = 0; c < NY; ++c) {
+        const double t = PC_SD_LU(k, c);
+        PC_SD_LU(k, c) = PC_SD_LU(p, c);
+        PC_SD_LU(p, c) = t;
+      }
+    const double d = PC_SD_LU(k, k);
+    if (!(best <= 1.7976931348623157e308) || d == 0.0) return false;
+#pragma unroll 1
+    for (int r = k + 1; r < NY; ++r) {
+      const double l = PC_SD_LU(r, k) / d;
+      PC_SD_LU(r, k) = l;
+      for (int c = k + 1; c < NY; ++c) PC_SD_LU(r, c) = PC_SD_LU(r, c) - l * PC_SD_LU(k, c);
+    }
+  }
+  return true;
+}
+
+// r <- W^-1 r from the factors: all row swaps first, then the unit lower and the upper triangle.  r stays in registers:
+// a swap with a run-time row is a chain of selects.
+template <int NY>
+__device__ __forceinline__ void stiff_solve(const double* lu, const int32_t* piv, int lane, double* r) {
+  static_for<0, NY>([&](auto k_) {
+    constexpr int k = decltype(k_)::value;
+    const int p = PC_SD_PIV(k);
+    static_for<k + 1, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      const double rk = r[k], ra = r[a];
+      r[k] = p == a ? ra : rk;
+      r[a] = p == a ? rk : ra;
+    });
+  });
+  static_for<0, NY>([&](auto k_) {
+    constexpr int k = decltype(k_)::value;
+    static_for<k + 1, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      r[a] = r[a] - PC_SD_LU(a, k) * r[k];
+    });
+  });
+  static_for<0, NY>([&](auto q_) {
+    constexpr int k = NY - 1 - decltype(q_)::value;
+    static_for<k + 1, NY>([&](auto c_) {
+      constexpr int c = decltype(c_)::value;
+      r[k] = r[k] - PC_SD_LU(k, c) * r[c];
+    });
+    r[k] = r[k] / PC_SD_LU(k, k);
+  });
+}
+
+// One attempt of width h from (c, y).  false: a Newton failure (ynew and err are then not set).  iters counts the
+// Newton iterations made.  err is the scaled norm of the filtered estimate (bad: it is not finite).
+template <class M>
+__device__ __forceinline__ bool stiff_step(const PcSolPropagateStiffArgs& A, double* lu, int32_t* piv, int lane, double* v,
+                                           const double* y, int64_t off, int n, double c, double h, double g, double* ynew,
+                                           double& err, bool& bad, int& iters) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NU = St::NU, NY1 = NY > 0 ? NY : 1, NJ = St::NJ, NFN = St::NFN;
+  double Ks[5][NY1], Kc[NY1];
+  const double hg = h * SD_GAMMA;
+  {
+    double F[NFN > 0 ? NFN : 1], Jv[NJ > 0 ? NJ : 1];
+    static_for<0, NY>([&](auto a_) { v[decltype(a_)::value] = y[decltype(a_)::value]; });
+    static_for<0, NU>([&](auto b_) {
+      constexpr int b = decltype(b_)::value;
+      v[NY + b] = sol_legendre(A.c.coef_u + (int64_t)b * A.c.NC + off, n, c);
+    });
+    M::eval_fj(v, F, Jv);
+    static_for<0, NY>([&](auto a_) { Kc[decltype(a_)::value] = g * F[decltype(a_)::value]; });
+    for (int e = 0; e < NY * NY; ++e) lu[e * PC_SOL_PROP_TB + lane] = 0.0;
+    static_for<0, NY>([&](auto a_) { PC_SD_LU(decltype(a_)::value, decltype(a_)::value) = 1.0; });
+    static_for<0, NJ>([&](auto e_) {
+      constexpr int e = decltype(e_)::value;
+      if constexpr (M::jr(e) < NY && M::jc(e) < NY)
+        PC_SD_LU(M::jr(e), M::jc(e)) = (M::jr(e) == M::jc(e) ? 1.0 : 0.0) - hg * (g * Jv[e]);
+    });
+  }
+  if (!stiff_factor<NY>(lu, piv, lane)) return false;
+  bool ok = true;
+  static_for<0, 5>([&](auto s_) {
+    constexpr int s = decltype(s_)::value;
+    // (no branch around a stage: a failed stage leaves the Newton loops of the later ones empty)
+    static_for<0, NU>([&](auto b_) {
+      constexpr int b = decltype(b_)::value;
+      v[NY + b] = sol_legendre(A.c.coef_u + (int64_t)b * A.c.NC + off, n, c + sd_c(s) * h);
+    });
+    double base[NY1];   // sum_{l<s} a_sl K_l, l ascending, zero entries of the tableau left out
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      double acc = 0.0;
+      static_for<0, s>([&](auto l_) {
+        constexpr int l = decltype(l_)::value;
+        constexpr double w = sd_a(s, l);
+        if constexpr (w != 0.0) acc += w * Ks[l][a];
+      });
+      base[a] = acc;
+    });
+    bool conv = false;
+    for (int it = 0; it < A.newton_max && !conv && ok; ++it) {
+      ++iters;
+      static_for<0, NY>([&](auto a_) {
+        constexpr int a = decltype(a_)::value;
+        v[a] = y[a] + h * (base[a] + SD_GAMMA * Kc[a]);
+      });
+      double F[NY1], r[NY1];
+      M::eval_f(v, F);
+      static_for<0, NY>([&](auto a_) { r[decltype(a_)::value] = g * F[decltype(a_)::value] - Kc[decltype(a_)::value]; });
+      stiff_solve<NY>(lu, piv, lane, r);
+      double theta = 0.0;
+      static_for<0, NY>([&](auto a_) {
+        constexpr int a = decltype(a_)::value;
+        Kc[a] += r[a];
+        const double q = fabs(hg * r[a]) / (A.atol[a] + A.rtol * fmax(fabs(y[a]), fabs(v[a])));
+        if (!(q <= 1.7976931348623157e308)) ok = false;   // NaN or inf (fmax would drop a NaN)
+        theta = fmax(theta, q);
+      });
+      conv = ok && theta <= SD_NEWTON_TOL;
+    }
+    if (!conv) ok = false;
+    static_for<0, NY>([&](auto a_) { Ks[s][decltype(a_)::value] = Kc[decltype(a_)::value]; });
+  });
+  if (!ok) return false;
+  double e[NY1];
+  static_for<0, NY>([&](auto a_) {
+    constexpr int a = decltype(a_)::value;
+    double acc = 0.0, ace = 0.0;
+    static_for<0, 5>([&](auto i_) {
+      constexpr int i = decltype(i_)::value;
+      constexpr double w = sd_a(4, i), we = sd_e(i);
+      if constexpr (w != 0.0) acc += w * Ks[i][a];
+      if constexpr (we != 0.0) ace += we * Ks[i][a];
+    });
+    ynew[a] = y[a] + h * acc;
+    e[a] = h * ace;
+  });
+  stiff_solve<NY>(lu, piv, lane, e);
+  err = 0.0;
+  bad = false;
+  static_for<0, NY>([&](auto a_) {
+    constexpr int a = decltype(a_)::value;
+    const double q = fabs(e[a]) / (A.atol[a] + A.rtol * fmax(fabs(y[a]), fabs(ynew[a])));
+    if (!(q <= 1.7976931348623157e308)) bad = true;
+    err = fmax(err, q);
+  });
+  return true;
+}
+
+template <class M>
+__device__ __forceinline__ void sol_propagate_stiff(const PcSolPropagateStiffArgs& A) {
+  using St = S<M>;
+  constexpr int NY = St::NY, NY1 = NY > 0 ? NY : 1;
+  if constexpr (NY <= PC_SOL_STIFF_MAX_NY) {
+    __shared__ double lu[NY1 * NY1 * PC_SOL_PROP_TB];
+    __shared__ int32_t piv[NY1 * PC_SOL_PROP_TB];
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n_seg || lane >= PC_SOL_PROP_TB) return;
+    const int N = A.v.N;
+    const int32_t* sec_s = A.v.sec_s;
+    const int j0 = A.seg_node[i], j1 = A.seg_node[i + 1];
+    int k = A.seg_sec[i];
+    double t0, tF;
+    sol_times<M>(A.v, t0, tF);
+    const double stretch = 0.5 * (tF - t0);
+    double v[St::NV > 0 ? St::NV : 1], y[NY1], ynew[NY1];
+    sol_params<M>(A.v, v);
+    static_for<0, NY>([&](auto a_) {
+      constexpr int a = decltype(a_)::value;
+      y[a] = A.c.node_y[(int64_t)a * N + j0];
+      if (j0 == 0) A.y_arrive[(int64_t)a * N] = y[a];
+    });
+    if (j0 == 0) A.accepted[0] = A.rejected[0] = A.newton_rejected[0] = A.newton_iterations[0] = 0;
+    const bool fixed = A.substeps > 0;
+    int status = -1;
+    for (int j = j0; j < j1; ++j) {
+      if (status >= 0) {   // behind the interval that failed
+        static_for<0, NY>([&](auto a_) { A.y_arrive[(int64_t) decltype(a_)::value * N + j + 1] = __builtin_nan(""); });
+        A.accepted[j + 1] = A.rejected[j + 1] = A.newton_rejected[j + 1] = A.newton_iterations[j + 1] = 0;
+        continue;
+      }
+      if (j >= sec_s[k + 1] && k < A.v.K - 1) ++k;
+      const int sk = sec_s[k], n = sec_s[k + 1] - sk + 1;
+      const int64_t off = (int64_t)sk + k;
+      const double ta = A.c.sec_tau[k], w = A.c.sec_tau[k + 1] - ta;
+      const double ca = 2.0 * (A.tau[j] - ta) / w - 1.0, cb = 2.0 * (A.tau[j + 1] - ta) / w - 1.0;
+      const double g = stretch * (0.5 * w);
+      int n_acc = 0, n_rej = 0, n_newt = 0, iters = 0;
+      const double h0 = fixed ? (cb - ca) / (double)A.substeps : cb - ca;
+      double c = ca, h = h0;
+      bool last = true, after_reject = false, done = false;
+      while (!done && (fixed || n_acc + n_rej < A.max_steps)) {
+        if (fixed) {   // step q starts at ca + q h0 (computed, not accumulated); the last one ends at cb
+          c = ca + (double)n_acc * h0;
+          h = n_acc == A.substeps - 1 ? cb - c : h0;
+        }
+        double err = 0.0;
+        bool bad = false;
+        const bool newton = stiff_step<M>(A, lu, piv, lane, v, y, off, n, c, h, g, ynew, err, bad, iters);
+        if (fixed) {
+          if (!newton) {
+            ++n_rej;
+            ++n_newt;
+            break;
+          }
+          ++n_acc;
+          static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
+          done = n_acc == A.substeps;
+          continue;
+        }
+        double factor = newton ? 0.2 : 0.25;
+        if (newton && !bad) factor = err == 0.0 ? 5.0 : fmin(5.0, fmax(0.2, 0.9 * pow(err, -0.25)));
+        if (newton && !bad && err <= 1.0) {
+          ++n_acc;
+          static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
+          c = last ? cb : c + h;
+          if (after_reject) factor = fmin(factor, 1.0);
+          after_reject = false;
+          const double rest = cb - c;
+          if (last || !(rest > 0.0)) {
+            done = true;
+          } else {
+            h *= factor;
+            last = h >= rest;
+            if (last) h = rest;
+          }
+        } else {
+          ++n_rej;
+          if (!newton) ++n_newt;
+          h *= factor;
+          last = false;
+          after_reject = true;
+        }
+      }
+      if (!done) status = j;
+      A.accepted[j + 1] = n_acc;
+      A.rejected[j + 1] = n_rej;
+      A.newton_rejected[j + 1] = n_newt;
+      A.newton_iterations[j + 1] = iters;
+      static_for<0, NY>([&](auto a_) {
+        constexpr int a = decltype(a_)::value;
+        A.y_arrive[(int64_t)a * N + j + 1] = status >= 0 ? __builtin_nan("") : y[a];
+      });
+    }
+    A.seg_status[i] = status;
+  }
+}
+#undef PC_SD_LU
+#undef PC_SD_PIV
+
 }  // namespace pc
 
 // the seven entry points of phase I, instantiated by the generated source once per phase (pc_mesh_err_p<i> is emitted by
@@ -1144,6 +1454,9 @@ __device__ __forceinline__ void mesh_error(const PcRefineArgs& A) {
   }                                                                                                          \
   extern "C" __global__ void __launch_bounds__(PC_SOL_PROP_TB) pc_sol_propagate_dense_p##I(PcSolPropagateDenseArgs a) { \
     pc::sol_propagate_dense<gen::Phase##I>(a);                                                               \
+  }                                                                                                          \
+  extern "C" __global__ void __launch_bounds__(PC_SOL_PROP_TB) pc_sol_propagate_stiff_p##I(PcSolPropagateStiffArgs a) { \
+    pc::sol_propagate_stiff<gen::Phase##I>(a);                                                               \
   }                                                                                                          \
   extern "C" __global__ void __launch_bounds__(256) pc_sol_multipliers_p##I(PcSolMultiplierArgs a) {         \
     pc::sol_multipliers<gen::Phase##I>(a);                                                                   \

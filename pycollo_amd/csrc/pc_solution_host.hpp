@@ -47,7 +47,8 @@ struct pc_solution {
     DevBuf<int32_t> dense_seg, dense_sec, dense_order, dense_q0;   // dense propagation: its own staged lists,
     DevBuf<double> dense_atol, dense_iatol, dense_tau_q;           // tolerances and sorted queries
     std::vector<double> h_tau;                   // the node abscissae on the host (the queries' slots are found in them)
-    hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr, fn_propagate = nullptr, fn_propagate_dense = nullptr;
+    hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr, fn_propagate = nullptr, fn_propagate_dense = nullptr,
+                  fn_propagate_stiff = nullptr;
     PcPhaseView view;       // the phase as of creation: what sampling, the costates and propagation unscale with
     PcSolCurves curves;     // the polynomials the fit kernel made
     int NY = 0, NU = 0, NQ = 0;
@@ -392,6 +393,45 @@ void solution_launch_propagate(pc_solution* s, int phase, int64_t n_seg, const i
   launch_block(S.fn_propagate, (unsigned)P.blocks, (unsigned)P.TB, 0, s->h->stream, a);
 }
 
+// pc_sol_propagate_stiff_p<phase> on the handle's stream; the outputs are device arrays ([n_y][N], [N], [N], [n_seg],
+// [N], [N])
+void solution_launch_propagate_stiff(pc_solution* s, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps,
+                                     double rtol, const double* atol, int64_t max_steps, int64_t newton_max, double* d_y,
+                                     int32_t* d_acc, int32_t* d_rej, int32_t* d_status, int32_t* d_newton_rej,
+                                     int32_t* d_newton_it) {
+  auto& S = *s->ph[phase];
+  pcs::check_propagate_stiff_options(substeps, rtol, atol, S.NY, max_steps, newton_max);
+  const pcs::PropagatePlan P = pcs::build_propagate_plan(S.plan, n_seg, seg_nodes);
+  if (!d_acc || !d_rej || !d_status || !d_newton_rej || !d_newton_it || (S.NY > 0 && !d_y))
+    throw std::runtime_error("propagate: null output");
+  if (!S.fn_propagate_stiff)
+    HIP_OK(find_fn(s->h, &S.fn_propagate_stiff, ("pc_sol_propagate_stiff_p" + std::to_string(phase)).c_str()));
+  HIP_OK(hipStreamSynchronize(s->h->stream));   // an earlier call may still read the staged lists
+  S.prop_seg.upload(P.seg_node);
+  S.prop_sec.upload(P.seg_sec);
+  S.prop_atol.upload(std::vector<double>(atol, atol + S.NY));
+  PcSolPropagateStiffArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.v = S.view;
+  a.c = S.curves;
+  a.tau = S.node_tau.p;
+  a.seg_node = S.prop_seg.p;
+  a.seg_sec = S.prop_sec.p;
+  a.atol = S.prop_atol.p;
+  a.y_arrive = d_y;
+  a.accepted = d_acc;
+  a.rejected = d_rej;
+  a.seg_status = d_status;
+  a.newton_rejected = d_newton_rej;
+  a.newton_iterations = d_newton_it;
+  a.rtol = rtol;
+  a.n_seg = P.n_seg;
+  a.substeps = (int32_t)substeps;
+  a.max_steps = (int32_t)max_steps;
+  a.newton_max = (int32_t)newton_max;
+  launch_block(S.fn_propagate_stiff, (unsigned)P.blocks, (unsigned)P.TB, 0, s->h->stream, a);
+}
+
 // pc_sol_propagate_dense_p<phase> on the handle's stream; the outputs are device arrays ([n_y][N], [N], [N], [n_seg],
 // [n_q][N], [n_y][n_query], [n_q][n_query]); the queries are tau, a host array
 void solution_launch_propagate_dense(pc_solution* s, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps,
@@ -710,6 +750,46 @@ int pc_solution_propagate_device(pc_solution* sol, int phase, int64_t n_seg, con
     (void)solution_phase(sol, phase);
     solution_launch_propagate(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, d_y_arrive, d_accepted, d_rejected,
                               d_seg_status);
+  });
+}
+
+int pc_solution_propagate_stiff(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
+                                const double* atol, int64_t max_steps, int64_t newton_max, double* y_arrive, int32_t* accepted,
+                                int32_t* rejected, int32_t* seg_status, int32_t* newton_rejected, int32_t* newton_iterations) {
+  return guarded(g_err, [&] {
+    auto& S = solution_phase(sol, phase);
+    if (!accepted || !rejected || !seg_status || !newton_rejected || !newton_iterations || (S.NY > 0 && !y_arrive))
+      throw std::runtime_error("propagate: null output");
+    if (n_seg < 1 || n_seg > (int64_t)S.plan.N - 1) throw std::runtime_error("propagate: the number of segments must be in [1, N - 1]");
+    const size_t N = (size_t)S.plan.N;
+    DevBuf<double> d_y;
+    DevBuf<int32_t> d_acc, d_rej, d_st, d_nr, d_ni;
+    d_y.alloc(N * (size_t)std::max(1, S.NY));
+    d_acc.alloc(N);
+    d_rej.alloc(N);
+    d_nr.alloc(N);
+    d_ni.alloc(N);
+    d_st.alloc((size_t)n_seg);
+    solution_launch_propagate_stiff(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, newton_max, d_y.p, d_acc.p,
+                                    d_rej.p, d_st.p, d_nr.p, d_ni.p);
+    HIP_OK(hipStreamSynchronize(sol->h->stream));
+    solution_down(y_arrive, d_y, N * S.NY);
+    HIP_OK(hipMemcpy(accepted, d_acc.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(rejected, d_rej.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(newton_rejected, d_nr.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(newton_iterations, d_ni.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(seg_status, d_st.p, (size_t)n_seg * sizeof(int32_t), hipMemcpyDeviceToHost));
+  });
+}
+
+int pc_solution_propagate_stiff_device(pc_solution* sol, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps,
+                                       double rtol, const double* atol, int64_t max_steps, int64_t newton_max, double* d_y_arrive,
+                                       int32_t* d_accepted, int32_t* d_rejected, int32_t* d_seg_status,
+                                       int32_t* d_newton_rejected, int32_t* d_newton_iterations) {
+  return guarded(g_err, [&] {
+    (void)solution_phase(sol, phase);
+    solution_launch_propagate_stiff(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, newton_max, d_y_arrive,
+                                    d_accepted, d_rejected, d_seg_status, d_newton_rejected, d_newton_iterations);
   });
 }
 

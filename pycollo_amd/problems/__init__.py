@@ -696,6 +696,33 @@ def function_family(family: str, K: int = 5, order: int = 4) -> ProblemSpec:
     return prob
 
 
+def stiff_relaxation(rate: float = 1e4, K: int = 5, order: int = 4) -> ProblemSpec:
+    """Prothero-Robinson relaxation onto a moving target, a stiff phase without controls for ``Solution.propagate``'s
+    implicit method: y1' = -rate (y1 - sin y2) + cos y2, y2' = 1 with y2(t0) = t0, so that y2 is the time.
+    Its flow is known: from (y1, y2)(a), y2(t) = y2(a) + t - a and
+    y1(t) = sin y2(t) + (y1(a) - sin y2(a)) exp(-rate (t - a)).  Fixed times [0, 2] (at rate 1e4 the shortest node
+    interval of the default mesh is 1100 relaxation times long, more than an explicit pair crosses in 256 steps), no
+    path constraints; the objective (the final y1) is only there because an NLP needs one."""
+    y1, y2 = sym.symbols("y1 y2", real=True)
+    prob = ProblemSpec("Stiff relaxation")
+    ph = prob.new_phase("A")
+    ph.state_variables = [y1, y2]
+    ph.control_variables = []
+    ph.state_equations = [-float(rate) * (y1 - sym.sin(y2)) + sym.cos(y2), sym.Integer(1)]
+    prob.objective_function = ph.final_state_variables[0]
+    ph.bounds.initial_time = 0.0
+    ph.bounds.final_time = 2.0
+    ph.bounds.state_variables = [[-2.0, 2.0], [-1.0, 3.0]]
+    ph.bounds.control_variables = []
+    ph.bounds.initial_state_constraints = {y1: [-2.0, 2.0], y2: 0.0}
+    ph.bounds.final_state_constraints = {y1: [-2.0, 2.0], y2: [-1.0, 3.0]}
+    ph.guess.time = np.array([0.0, 2.0])
+    ph.guess.state_variables = np.array([[0.0, np.sin(2.0)], [0.0, 2.0]])
+    ph.guess.control_variables = np.zeros((0, 2))
+    _mesh(ph, K, order)
+    return prob
+
+
 FUNCTION_FAMILIES = ("powers", "trig", "special", "kinks")
 
 
@@ -714,6 +741,7 @@ REGISTRY = {
     "tumour_anti_angiogenesis": tumour_anti_angiogenesis,
     "space_station": space_station,
     "function_family": function_family,
+    "stiff_relaxation": stiff_relaxation,
 }
 
 

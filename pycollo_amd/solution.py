@@ -145,6 +145,9 @@ def solution_tables(method: str, n: int):
 
 
 PROPAGATE_MAX_STEPS = 1 << 20           # csrc/pc_args.h PC_SOL_PROP_MAX_STEPS
+PROPAGATE_METHODS = ("dopri5", "sdirk4")
+PROPAGATE_STIFF_MAX_NY = 11             # csrc/pc_args.h PC_SOL_STIFF_MAX_NY
+PROPAGATE_STIFF_MAX_NEWTON = 32         # csrc/pc_args.h PC_SOL_STIFF_MAX_NEWTON
 
 
 @dataclasses.dataclass
@@ -155,7 +158,9 @@ class Propagation:
     the state's scale V_a of the engine's scaling; ``terminal_defect`` [n_y]: the last column of ``defect``.
     ``accepted`` / ``rejected`` [N]: the steps of the interval that ends at the node.  ``segments`` [n_seg + 1]: the
     node every segment starts at, and N - 1.  ``status`` [n_seg]: -1, or the first node of the interval that used up
-    ``max_steps`` (arrivals from there to the segment's end are NaN); ``ok`` = ``status == -1``."""
+    ``max_steps`` (arrivals from there to the segment's end are NaN); ``ok`` = ``status == -1``.
+    ``newton_rejected`` / ``newton_iterations`` [N] (``method="sdirk4"``; ``None`` otherwise): the rejected steps of the
+    interval whose cause was a Newton failure (they count in ``rejected`` too), and all its Newton iterations."""
     y: object
     defect: object
     relative_defect: object
@@ -165,6 +170,8 @@ class Propagation:
     status: object
     ok: object
     terminal_defect: object
+    newton_rejected: object = None
+    newton_iterations: object = None
 
 
 @dataclasses.dataclass
@@ -271,6 +278,21 @@ def check_propagate_tolerances(substeps, rtol, atol, max_steps):
         raise ValueError("every atol must be finite and positive")
     if int(max_steps) != max_steps or not 1 <= max_steps <= PROPAGATE_MAX_STEPS:
         raise ValueError("max_steps must be an integer in [1, 2^20]")
+
+
+def check_propagate_method(method, newton_max, rtol, n_y: int):
+    """The further refusals of ``Solution.propagate(method=...)`` (csrc/pc_propagate_plan.hpp makes the same ones for
+    the implicit method)."""
+    if method not in PROPAGATE_METHODS:
+        raise ValueError(f"method must be one of {PROPAGATE_METHODS}, not {method!r}")
+    if method == "dopri5":
+        return
+    if int(newton_max) != newton_max or not 1 <= newton_max <= PROPAGATE_STIFF_MAX_NEWTON:
+        raise ValueError(f"newton_max must be an integer in [1, {PROPAGATE_STIFF_MAX_NEWTON}]")
+    if not (np.isfinite(rtol) and rtol > 0):
+        raise ValueError('rtol must be finite and positive (method="sdirk4" reads it in both modes)')
+    if n_y > PROPAGATE_STIFF_MAX_NY:
+        raise ValueError(f'method="sdirk4" takes phases of at most {PROPAGATE_STIFF_MAX_NY} states, this one has {n_y}')
 
 
 def _is_torch(t) -> bool:
@@ -491,6 +513,9 @@ class Solution:
         prop = [vp, C.c_int, C.c_int64, vp, C.c_int64, C.c_double, vp, C.c_int64, vp, vp, vp, vp]
         lib.pc_solution_propagate.argtypes = prop
         lib.pc_solution_propagate_device.argtypes = prop
+        stiff = prop[:8] + [C.c_int64] + [vp] * 6
+        lib.pc_solution_propagate_stiff.argtypes = stiff
+        lib.pc_solution_propagate_stiff_device.argtypes = stiff
         dense = [vp, C.c_int, C.c_int64, vp, C.c_int64, C.c_double, vp, vp, C.c_int64, C.c_int64, vp] + [vp] * 7
         lib.pc_solution_propagate_dense.argtypes = dense
         lib.pc_solution_propagate_dense_device.argtypes = dense
@@ -877,7 +902,8 @@ class Solution:
         V = self.engine.layout.expand_x(self.engine.V_ocp)
         return np.array([V[pl.x_off + a * pl.N] for a in range(pl.n_y)], dtype=np.float64)
 
-    def propagate(self, phase: int, *, restart="nodes", rtol: float = 1e-9, atol=None, substeps=None, max_steps: int = 4096):
+    def propagate(self, phase: int, *, restart="nodes", rtol: float = 1e-9, atol=None, substeps=None, max_steps: int = 4096,
+                  method: str = "dopri5", newton_max: int = 8):
         """Integrate the dynamics forward under the solution's controls (``pc_sol_propagate_p<i>``) and
         return a :class:`Propagation`.
 
@@ -896,6 +922,13 @@ class Solution:
         ``max_steps`` (accepted + rejected per interval, 1 .. 2^20) bounds the work: a segment whose interval uses it up
         stops there (``ok`` False, NaN from that interval to the segment's end); the other segments are unaffected.
 
+        ``method="sdirk4"`` (``pc_sol_propagate_stiff_p<i>``) is for stiff phases, where stability and not
+        accuracy sets the explicit pair's step: the five-stage L-stable SDIRK method of order 4 (Hairer & Wanner), one
+        Jacobian and one LU factorisation per attempt, a Newton iteration per stage of at most ``newton_max`` (1 .. 32)
+        iterations, stopped by ``rtol`` and ``atol`` -- so ``rtol`` is read and checked in both modes.  A Newton failure
+        rejects the step (adaptive) or ends the segment there (fixed); ``newton_rejected`` and ``newton_iterations``
+        of the result count them.  Phases of up to 11 states.  ``"dopri5"`` is the default and ignores ``newton_max``.
+
         NumPy out, unless ``restart`` or ``atol`` is a torch device tensor: then torch tensors on that device.  Bad
         arguments raise ``ValueError`` before anything is launched."""
         phase = self._phase(phase, need_handle=False)
@@ -911,31 +944,49 @@ class Solution:
                 atol = atol.detach().cpu().numpy()
             at = np.ascontiguousarray(np.broadcast_to(np.asarray(atol, dtype=np.float64), (n_y,)))
         check_propagate_tolerances(substeps, rtol, at, max_steps)
+        check_propagate_method(method, newton_max, rtol, n_y)
+        stiff = method == "sdirk4"
         at = np.ascontiguousarray(at, dtype=np.float64)
         self._phase(phase)     # (the device is needed from here on)
         n_seg, m = len(seg) - 1, 0 if substeps is None else int(substeps)
         head = (self._h, phase, n_seg, seg.ctypes.data, m, float(rtol), at.ctypes.data if n_y else None, int(max_steps))
+        if stiff:
+            head += (int(newton_max),)
+        nrej = nit = None
         if device is not None:
             import torch
             y = torch.empty((n_y, N), dtype=torch.float64, device=device)
             acc, rej = (torch.empty((N,), dtype=torch.int32, device=device) for _ in range(2))
             status = torch.empty((n_seg,), dtype=torch.int32, device=device)
             torch.cuda.current_stream(device).synchronize()     # the handle's stream is not torch's
-            self._check(self._lib.pc_solution_propagate_device(*head, y.data_ptr() if n_y else None, acc.data_ptr(),
-                                                               rej.data_ptr(), status.data_ptr()))
+            if stiff:
+                nrej, nit = (torch.empty((N,), dtype=torch.int32, device=device) for _ in range(2))
+                self._check(self._lib.pc_solution_propagate_stiff_device(*head, y.data_ptr() if n_y else None, acc.data_ptr(),
+                                                                         rej.data_ptr(), status.data_ptr(), nrej.data_ptr(),
+                                                                         nit.data_ptr()))
+            else:
+                self._check(self._lib.pc_solution_propagate_device(*head, y.data_ptr() if n_y else None, acc.data_ptr(),
+                                                                   rej.data_ptr(), status.data_ptr()))
             self._check(self._lib.pc_synchronize(self.engine._h))
             node_y = torch.as_tensor(np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N), device=device)
             scale = torch.as_tensor(V, device=device)[:, None]
         else:
             y = np.empty((n_y, N))
             acc, rej, status = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32), np.empty(n_seg, dtype=np.int32)
-            self._check(self._lib.pc_solution_propagate(*head, y.ctypes.data if n_y else None, acc.ctypes.data, rej.ctypes.data,
-                                                        status.ctypes.data))
+            if stiff:
+                nrej, nit = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32)
+                self._check(self._lib.pc_solution_propagate_stiff(*head, y.ctypes.data if n_y else None, acc.ctypes.data,
+                                                                  rej.ctypes.data, status.ctypes.data, nrej.ctypes.data,
+                                                                  nit.ctypes.data))
+            else:
+                self._check(self._lib.pc_solution_propagate(*head, y.ctypes.data if n_y else None, acc.ctypes.data,
+                                                            rej.ctypes.data, status.ctypes.data))
             node_y = np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N)
             scale = V[:, None]
         defect = y - node_y
         return Propagation(y=y, defect=defect, relative_defect=defect / scale, accepted=acc, rejected=rej, segments=seg,
-                           status=status, ok=status == -1, terminal_defect=defect[:, -1])
+                           status=status, ok=status == -1, terminal_defect=defect[:, -1], newton_rejected=nrej,
+                           newton_iterations=nit)
 
     def propagate_dense(self, phase: int, t=None, *, tau=None, restart="nodes", rtol: float = 1e-9, atol=None,
                         integral_atol=None, substeps=None, max_steps: int = 4096):
