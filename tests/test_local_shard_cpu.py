@@ -5,6 +5,7 @@ evaluation happens here (no GPU); tests/test_gpu_local_shard.py runs the kernels
 import numpy as np
 import pytest
 
+import shard_edges
 from pycollo_amd import problems
 from pycollo_amd.engine import NlpEngine
 from pycollo_amd.sharding import LocalShard, ShardPlan, global_tile_plan
@@ -29,8 +30,27 @@ def test_local_pattern_is_the_global_pattern_of_the_owned_rows(built, name, kw, 
     prob = problems.REGISTRY[name](**kw)
     if ragged:
         prob = _ragged(prob)
-    g = NlpEngine(prob, device=None)
+    _check_local_pattern(prob, world)
+
+
+@pytest.mark.parametrize("case", shard_edges.IDS)
+def test_local_pattern_where_a_ranks_share_degenerates(built, monkeypatch, case):
+    """The same at the partitions of tests/shard_edges.py: idle ranks, ranks with tiles in some phases only, ranks of
+    one tile (first, interior, last), 2-node halo sections, Radau tables, a mixed build -- and each case is held to the
+    situation it is listed for."""
+    shard_edges.set_environment(monkeypatch)
+    _check_local_pattern(shard_edges.make_problem(case), shard_edges.world_of(case), shard_edges.mixed_of(case), case)
+
+
+def _check_local_pattern(prob, world, mixed=None, edge_case=None):
+    g = NlpEngine(prob, device=None, **({"mixed": mixed} if mixed else {}))
     plan = ShardPlan(g, world)
+    tile_plan = global_tile_plan(g.model, g.meshes, mixed=g.mixed, orders=g.orders) if edge_case else None
+    if edge_case:
+        shard_edges.check_situation(edge_case, plan, g.meshes, g.model)
+        for ip in range(len(g.model.phases)):     # the plan-only handle cut what the whole-NLP handle cut
+            np.testing.assert_array_equal(tile_plan["tiles"][ip][0], g.phase_tiles(ip)[0])
+            np.testing.assert_array_equal(tile_plan["tiles"][ip][1], g.phase_tile_orders(ip))
     gr, gc = g.evaluate_G_structure()
     hr, hc = g.evaluate_H_structure()
     oG, oH = g.num_c, g.num_c + g.nnz_jac
@@ -41,8 +61,15 @@ def test_local_pattern_is_the_global_pattern_of_the_owned_rows(built, name, kw, 
         a_, b_ = int(px[r_]), int(px[c_])
         point_pairs.add((max(a_, b_), min(a_, b_)))
     for r in range(world):
-        ls = LocalShard(prob, r, world, device=None)
+        ls = (LocalShard(g.model, r, world, device=None, meshes=g.meshes, plan=tile_plan) if edge_case
+              else LocalShard(prob, r, world, device=None))
         e = ls.engine
+        assert ls.length == plan.lengths[r]
+        if edge_case:     # (a phase without tiles of the rank: one section, nothing owned, no halo)
+            assert [te > tb for tb, te in ls.ranges] == [te > tb for tb, te in plan.tile_ranges[r]]
+            for ip, (tb, te) in enumerate(ls.ranges):
+                if te <= tb:
+                    assert (e.meshes[ip].K, ls.halo[ip], ls.halo_after[ip]) == (1, 0, 0)
         # same tiles as the global plan's range, behind the halo tile
         for ip, (tb, te) in enumerate(ls.ranges):
             k0g = plan.tiles[ip][0]

@@ -127,18 +127,36 @@ def _worker(rank, world, port, name, kw, q, root=None, mode="single"):
                                                ("two_phase_transfer", dict(K=40, order=4), 1, "split"),
                                                ("shuttle", dict(K=90, order=4, ragged=True), None, "unpadded")])     # all-gatherv
 def test_exchange_world2_gloo(built, name, kw, root, mode):
+    _exchange_gloo(2, name, kw, root, mode)
+
+
+# order 2, 30 sections: two tiles for three ranks -- rank 1 owns nothing (a solved mesh of a few hundred nodes is sharded like
+# this): it sends nothing, and as the only idle rank it still receives everything
+@pytest.mark.parametrize("name,kw,world,root,mode", [("hypersensitive", dict(K=30, order=2), 3, None, "unpadded"),
+                                                     ("hypersensitive", dict(K=30, order=2), 3, 2, "split")])
+def test_exchange_with_an_idle_rank_gloo(built, name, kw, world, root, mode):
+    from pycollo_amd.engine import NlpEngine
+    from pycollo_amd.sharding import ShardPlan
+    eng = NlpEngine(problems.REGISTRY[name](**kw), device=None)
+    lengths = ShardPlan(eng, world).lengths
+    eng.close()
+    assert min(lengths) == 0 and max(lengths) > 0       # the point of these lines: a rank without a share
+    _exchange_gloo(world, name, kw, root, mode)
+
+
+def _exchange_gloo(world, name, kw, root, mode):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, name, kw, q, root, mode)) for r in range(2)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, name, kw, q, root, mode)) for r in range(world)]
     for p in procs:
         p.start()
     for p in procs:
         p.join(timeout=180)
         assert p.exitcode == 0
-    results = dict(q.get(timeout=10) for _ in range(2))
-    assert results == {0: True, 1: True}
+    results = dict(q.get(timeout=10) for _ in range(world))
+    assert results == {r: True for r in range(world)}
 
 
 def test_shares_are_balanced_by_nodes_on_a_refined_mesh(built):
