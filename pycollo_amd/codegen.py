@@ -612,7 +612,7 @@ def _preload_count() -> int:
 
 def _kernels_stamp() -> str:
     h = hashlib.sha256()
-    for fn in ("pc_kernels.hpp", "pc_solution.hpp", "pc_args.h"):
+    for fn in ("pc_kernels.hpp", "pc_solution.hpp", "pc_step_control.hpp", "pc_args.h"):
         with open(os.path.join(CSRC, fn), "rb") as f:
             h.update(f.read())
     with open(os.path.abspath(__file__), "rb") as f:   # the generator itself: printer rules, kernel entry points

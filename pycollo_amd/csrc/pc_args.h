@@ -478,10 +478,11 @@ struct PcSolOptimalitySampleArgs {
 };
 
 // Arguments of the forward propagation (pc_solution.hpp, "propagation"): the dynamics integrated under the
-// solution's control interpolant by Dormand-Prince 5(4), one lane per segment of consecutive node intervals.
+// solution's control interpolant, one lane per segment of consecutive node intervals.  PcSolPropCommon is what the walk
+// over the node intervals (prop_walk) reads; the three kernels' blocks start with it and add what their method needs.
 #define PC_SOL_PROP_TB 64              // lanes of a workgroup of pc_sol_propagate
 #define PC_SOL_PROP_MAX_STEPS 1048576  // largest max_steps and largest substeps (2^20): every loop of the kernel is bounded
-struct PcSolPropagateArgs {
+struct PcSolPropCommon {
   PcPhaseView v;            // (x: the free times; the q / t / s arguments of f)
   PcSolCurves c;            // (node_y: where every segment starts)
   const double* tau;        // [N] node abscissae
@@ -490,62 +491,45 @@ struct PcSolPropagateArgs {
   const double* atol;       // [NY]
   double* y_arrive;         // [NY][N] column j >= 1: the state arriving at node j; column 0: y(0)
   int32_t* accepted;        // [N] steps of the interval that ends at the node (column 0: 0)
-  int32_t* rejected;        // [N]
-  int32_t* seg_status;      // [n_seg] -1: complete, else the first node of the interval that used up max_steps
+  int32_t* rejected;        // [N] (the implicit method: error rejections and Newton failures)
+  int32_t* seg_status;      // [n_seg] -1: complete, else the first node of the interval that used up max_steps or, in the
+                            //   implicit method's fixed mode, whose Newton iteration failed
   double rtol;
   int32_t n_seg, substeps, max_steps, reserved;   // substeps 0: adaptive
 };
 
-// Arguments of the propagation with integrals and dense output (pc_solution.hpp, pc_sol_propagate_dense):
-// the lane of PcSolPropagateArgs carries the NQ integrals of the phase beside the state and answers the queries its
-// node intervals own.  The queries are sorted by tau on the host (pc_propagate_plan.hpp): sorted query k is the
-// caller's query q_order[k]; slot 0 (sorted queries node_q0[0] .. node_q0[1]) holds the queries at tau_0, slot j >= 1
-// (node_q0[j] .. node_q0[j+1]) those in (tau_{j-1}, tau_j], answered by the lane that integrates that interval.
+// Dormand-Prince 5(4), the states only (pc_sol_propagate).
+struct PcSolPropagateArgs {
+  PcSolPropCommon p;
+};
+
+// Propagation with integrals and dense output (pc_sol_propagate_dense): the lane of pc_sol_propagate carries
+// the NQ integrals of the phase beside the state and answers the queries its node intervals own.  The queries are
+// sorted by tau on the host (pc_propagate_plan.hpp): sorted query k is the caller's query q_order[k]; slot 0 (sorted
+// queries node_q0[0] .. node_q0[1]) holds the queries at tau_0, slot j >= 1 (node_q0[j] .. node_q0[j+1]) those in
+// (tau_{j-1}, tau_j], answered by the lane that integrates that interval.
 struct PcSolPropagateDenseArgs {
-  PcPhaseView v;
-  PcSolCurves c;
-  const double* tau;           // [N]
-  const int32_t* seg_node;     // [n_seg+1]
-  const int32_t* seg_sec;      // [n_seg]
-  const double* atol;          // [NY]
+  PcSolPropCommon p;
   const double* integral_atol; // [NQ], or null: the integrals take no part in the error norm
   const double* tau_q;         // [Q] the queries' tau, ascending
   const int32_t* q_order;      // [Q] the caller's index of sorted query k
   const int32_t* node_q0;      // [N+1]
-  double* y_arrive;            // [NY][N] as in PcSolPropagateArgs, like the next three
-  int32_t* accepted;           // [N]
-  int32_t* rejected;           // [N]
-  int32_t* seg_status;         // [n_seg]
   double* q_arrive;            // [NQ][N] column j >= 1: the segment's integral arriving at node j; column 0: 0
   double* y_dense;             // [NY][Q] in the caller's query order
   double* q_dense;             // [NQ][Q]
-  double rtol;
   int64_t Q;
-  int32_t n_seg, substeps, max_steps, reserved;
 };
 
-// Arguments of the implicit propagation (pc_solution.hpp, pc_sol_propagate_stiff): the segments, tolerances
-// and outputs of PcSolPropagateArgs, integrated by the L-stable SDIRK method of order 4 with a Newton iteration per
-// stage.  A lane keeps the LU factors of its NY x NY iteration matrix and their row swaps in LDS, element e of lane l at
-// [e * PC_SOL_PROP_TB + l]: NY^2 doubles and NY int32 per lane, which is what bounds NY.
+// Implicit propagation (pc_sol_propagate_stiff): the L-stable SDIRK method of order 4 with a Newton
+// iteration per stage.  A lane keeps the LU factors of its NY x NY iteration matrix and their row swaps in LDS, element e
+// of lane l at [e * PC_SOL_PROP_TB + l]: NY^2 doubles and NY int32 per lane, which is what bounds NY.
 #define PC_SOL_STIFF_MAX_NY 11         // 11^2 * 512 B of factors + 11 * 256 B of row swaps = 64 768 B <= 64 KiB of static LDS
 #define PC_SOL_STIFF_MAX_NEWTON 32     // largest newton_max
 struct PcSolPropagateStiffArgs {
-  PcPhaseView v;
-  PcSolCurves c;
-  const double* tau;           // [N]
-  const int32_t* seg_node;     // [n_seg+1]
-  const int32_t* seg_sec;      // [n_seg]
-  const double* atol;          // [NY]
-  double* y_arrive;            // [NY][N] as in PcSolPropagateArgs, like the next three
-  int32_t* accepted;           // [N]
-  int32_t* rejected;           // [N] error rejections and Newton failures
-  int32_t* seg_status;         // [n_seg] -1: complete, else the first node of the interval that used up max_steps or,
-                               //   in fixed mode, whose Newton iteration failed
+  PcSolPropCommon p;
   int32_t* newton_rejected;    // [N] the rejected steps of the interval whose cause was a Newton failure (column 0: 0)
   int32_t* newton_iterations;  // [N] all Newton iterations of the interval, those of rejected steps included
-  double rtol;
-  int32_t n_seg, substeps, max_steps, newton_max;   // substeps 0: adaptive
+  int32_t newton_max, reserved;
 };
 
 #endif  // PC_ARGS_H

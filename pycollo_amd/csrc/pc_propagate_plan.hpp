@@ -4,7 +4,9 @@
 // (pc_solution_plan.hpp).  For pc_sol_propagate_dense also the check of integral_atol and the queries: their
 // checks, their stable sort and the slot of every query (tests/c/propagate_dense_plan_sanitize.cpp).  For
 // pc_sol_propagate_stiff the check of its options and the lane's LDS indexing
-// (tests/c/propagate_stiff_plan_sanitize.cpp).
+// (tests/c/propagate_stiff_plan_sanitize.cpp).  The three kernels share one plan, one set of staged lists and the
+// argument prefix PcSolPropCommon (pc_solution_host.hpp: solution_stage_propagate); the step control of a node interval
+// is host-testable too, in a header of its own (pc_step_control.hpp, tests/c/step_control_sanitize.cpp).
 #ifndef PC_PROPAGATE_PLAN_HPP
 #define PC_PROPAGATE_PLAN_HPP
 

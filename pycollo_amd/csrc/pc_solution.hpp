@@ -10,6 +10,8 @@
 #ifndef PC_SOLUTION_HPP
 #define PC_SOLUTION_HPP
 
+#include "pc_step_control.hpp"
+
 namespace pc {
 
 // ---- what the kernels share: unscaling through the phase view, the lanes of a tile, the table contraction ----
@@ -617,6 +619,9 @@ __device__ __forceinline__ void sol_sample_optimality(const PcSolOptimalitySampl
 // section's first node) and writes, at the node every interval ends at, the arriving state and the interval's step
 // counts: its own columns only.  No step straddles a node.  No LDS, no atomics; the seven stage vectors live in
 // registers (7 NY doubles), which is why a workgroup is one wave: many small workgroups spread over the CUs.
+// The walk is prop_walk, for this kernel and pc_sol_propagate_dense alike; each of the two is a method handed to it
+// (pc_sol_propagate_stiff still carries its own copy, see there).  The steps of an interval are placed by StepControl
+// (pc_step_control.hpp):
 //   fixed (substeps = m >= 1): step i of an interval starts at c_j + i h, h = (c_{j+1} - c_j) / m, and has width h (the
 //     last one: c_{j+1} - its start).  Six stages: the seventh only feeds the error estimate.
 //   adaptive (substeps = 0): h starts as the whole interval; err = max_a |e_a| / (atol_a + rtol max(|y_a|, |ynew_a|));
@@ -739,106 +744,117 @@ __device__ __forceinline__ void prop_err(const double (&Ks)[7][N1], const double
   });
 }
 
-// One step: prop_stages without integrals.  ERR: the seventh stage and err, the scaled error norm (bad: it is not
-// finite).
-template <class M, bool ERR>
-__device__ __forceinline__ void prop_step(const PcSolPropagateArgs& A, double* v, const double* y, int64_t off, int n, double c,
-                                          double h, double g, double* ynew, double& err, bool& bad) {
-  using St = S<M>;
-  constexpr int NY = St::NY, NY1 = NY > 0 ? NY : 1;
-  double Ks[7][NY1], Gs[7][1];
-  prop_stages<M, ERR, 0>(A, v, y, nullptr, off, n, c, h, g, false, Ks, Gs, ynew, nullptr);
-  if constexpr (ERR) {
-    err = 0.0;
-    bad = false;
-    prop_err<NY, NY1>(Ks, y, ynew, h, A.atol, A.rtol, err, bad);
-  }
-}
+// One node interval of a lane's walk: its section's slice of the coefficient arrays (n per control from off), the
+// section's start and width in tau (a point's c is 2 (tau - ta) / w - 1), the interval's ends in c, g = stretch w_k / 2.
+struct PropInterval {
+  int64_t off;
+  int n;
+  double ta, w, ca, cb, g;
+};
 
-template <class M>
-__device__ __forceinline__ void sol_propagate(const PcSolPropagateArgs& A) {
+// The walk of one lane over the node intervals of its segment, for every method: the start from the node value and
+// column 0, the section step, the interval's constants, the steps StepControl places (pc_step_control.hpp), what is
+// behind a failure, the arriving columns and seg_status.  The method supplies
+//   Control                                        its constants for StepControl;
+//   start(first, y)                                its own state at the segment's start; first: its writes to column 0;
+//   open(j)                                        before interval (j, j+1), run or not;
+//   attempt<FIXED>(iv, v, y, c, h, ce, ynew, err, bad)   one attempt of width h from (c, y) that ends at ce: ynew and, in
+//                                                  adaptive mode, err and bad; false: a Newton failure;
+//   accept(iv, y, ynew, c, h, ce)                  the attempt was accepted, before y becomes ynew;
+//   arrive(j, ctl, failed)                         its own columns at node j + 1 (failed: at or behind a failure, where
+//                                                  ctl's counts are zero behind it).
+template <class M, class Method>
+__device__ __forceinline__ void prop_walk(const PcSolPropCommon& P, Method& mth) {
   using St = S<M>;
   constexpr int NY = St::NY, NY1 = NY > 0 ? NY : 1;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.n_seg) return;
-  const int N = A.v.N;
-  const int32_t* sec_s = A.v.sec_s;
-  const int j0 = A.seg_node[i], j1 = A.seg_node[i + 1];
-  int k = A.seg_sec[i];
+  if (i >= P.n_seg) return;
+  const int N = P.v.N;
+  const int32_t* sec_s = P.v.sec_s;
+  const int j0 = P.seg_node[i], j1 = P.seg_node[i + 1];
+  int k = P.seg_sec[i];
   double t0, tF;
-  sol_times<M>(A.v, t0, tF);
+  sol_times<M>(P.v, t0, tF);
   const double stretch = 0.5 * (tF - t0);
   double v[St::NV > 0 ? St::NV : 1], y[NY1], ynew[NY1];
-  sol_params<M>(A.v, v);
+  sol_params<M>(P.v, v);
   static_for<0, NY>([&](auto a_) {
     constexpr int a = decltype(a_)::value;
-    y[a] = A.c.node_y[(int64_t)a * N + j0];
-    if (j0 == 0) A.y_arrive[(int64_t)a * N] = y[a];
+    y[a] = P.c.node_y[(int64_t)a * N + j0];
+    if (j0 == 0) P.y_arrive[(int64_t)a * N] = y[a];
   });
-  if (j0 == 0) A.accepted[0] = A.rejected[0] = 0;
+  if (j0 == 0) P.accepted[0] = P.rejected[0] = 0;
+  mth.start(j0 == 0, y);
   int status = -1;
+  StepControl<typename Method::Control> ctl;
   for (int j = j0; j < j1; ++j) {
+    mth.open(j);
     if (status >= 0) {   // behind the interval that failed
-      static_for<0, NY>([&](auto a_) { A.y_arrive[(int64_t) decltype(a_)::value * N + j + 1] = __builtin_nan(""); });
-      A.accepted[j + 1] = A.rejected[j + 1] = 0;
-      continue;
-    }
-    if (j >= sec_s[k + 1] && k < A.v.K - 1) ++k;
-    const int sk = sec_s[k], n = sec_s[k + 1] - sk + 1;
-    const int64_t off = (int64_t)sk + k;
-    const double ta = A.c.sec_tau[k], w = A.c.sec_tau[k + 1] - ta;
-    const double ca = 2.0 * (A.tau[j] - ta) / w - 1.0, cb = 2.0 * (A.tau[j + 1] - ta) / w - 1.0;
-    const double g = stretch * (0.5 * w);
-    int n_acc = 0, n_rej = 0;
-    double err = 0.0;
-    bool bad = false;
-    if (A.substeps > 0) {
-      const int m = A.substeps;
-      const double h = (cb - ca) / (double)m;
-      for (int q = 0; q < m; ++q) {
-        const double c = ca + (double)q * h;
-        prop_step<M, false>(A, v, y, off, n, c, q == m - 1 ? cb - c : h, g, ynew, err, bad);
-        static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
-      }
-      n_acc = m;
+      ctl.clear();
     } else {
-      double c = ca, h = cb - ca;
-      bool last = true, after_reject = false, done = false;
-      while (!done && n_acc + n_rej < A.max_steps) {
-        prop_step<M, true>(A, v, y, off, n, c, h, g, ynew, err, bad);
-        double factor = 0.2;
-        if (!bad) factor = err == 0.0 ? 5.0 : fmin(5.0, fmax(0.2, 0.9 * pow(err, -0.2)));
-        if (!bad && err <= 1.0) {
-          ++n_acc;
-          static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
-          c = last ? cb : c + h;
-          if (after_reject) factor = fmin(factor, 1.0);
-          after_reject = false;
-          const double rest = cb - c;
-          if (last || !(rest > 0.0)) {
-            done = true;
-          } else {
-            h *= factor;
-            last = h >= rest;
-            if (last) h = rest;
-          }
-        } else {
-          ++n_rej;
-          h *= factor;
-          last = false;
-          after_reject = true;
+      if (j >= sec_s[k + 1] && k < P.v.K - 1) ++k;
+      const int sk = sec_s[k];
+      PropInterval iv;
+      iv.n = sec_s[k + 1] - sk + 1;
+      iv.off = (int64_t)sk + k;
+      iv.ta = P.c.sec_tau[k];
+      iv.w = P.c.sec_tau[k + 1] - iv.ta;
+      iv.ca = 2.0 * (P.tau[j] - iv.ta) / iv.w - 1.0;
+      iv.cb = 2.0 * (P.tau[j + 1] - iv.ta) / iv.w - 1.0;
+      iv.g = stretch * (0.5 * iv.w);
+      auto steps = [&](auto fixed_) {   // a loop per mode: the attempt knows the mode at compile time
+        if (fixed_) ctl.start_fixed(iv.ca, iv.cb, P.substeps);
+        else ctl.start_adaptive(iv.ca, iv.cb);
+        while (ctl.more(P.max_steps)) {
+          const double c = ctl.c, h = ctl.h, ce = ctl.end();
+          double err = 0.0;
+          bool bad = false;
+          const bool newton_ok = mth.template attempt<decltype(fixed_)::value>(iv, v, y, c, h, ce, ynew, err, bad);
+          ctl.report(newton_ok, bad, err, [&]() {
+            mth.accept(iv, y, ynew, c, h, ce);
+            static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
+          });
         }
-      }
-      if (!done) status = j;
+      };
+      if (P.substeps > 0) steps(std::true_type{});
+      else steps(std::false_type{});
+      if (ctl.failed()) status = j;
     }
-    A.accepted[j + 1] = n_acc;
-    A.rejected[j + 1] = n_rej;
+    P.accepted[j + 1] = ctl.n_acc;
+    P.rejected[j + 1] = ctl.n_rej;
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
-      A.y_arrive[(int64_t)a * N + j + 1] = status >= 0 ? __builtin_nan("") : y[a];
+      P.y_arrive[(int64_t)a * N + j + 1] = status >= 0 ? __builtin_nan("") : y[a];
     });
+    mth.arrive(j, ctl, status >= 0);
   }
-  A.seg_status[i] = status;
+  P.seg_status[i] = status;
+}
+
+// pc_sol_propagate: prop_stages without integrals; the seventh stage and the error norm in adaptive mode only.
+template <class M>
+struct PropDopri5 {
+  using Control = StepDopri5;
+  static constexpr int NY = S<M>::NY, NY1 = NY > 0 ? NY : 1;
+  const PcSolPropCommon& P;
+  __device__ __forceinline__ void start(bool, const double*) {}
+  __device__ __forceinline__ void open(int) {}
+  template <bool FIXED>
+  __device__ __forceinline__ bool attempt(const PropInterval& iv, double* v, const double* y, double c, double h, double,
+                                          double* ynew, double& err, bool& bad) {
+    double Ks[7][NY1], Gs[7][1];
+    prop_stages<M, !FIXED, 0>(P, v, y, nullptr, iv.off, iv.n, c, h, iv.g, false, Ks, Gs, ynew, nullptr);
+    if constexpr (!FIXED) prop_err<NY, NY1>(Ks, y, ynew, h, P.atol, P.rtol, err, bad);
+    return true;
+  }
+  __device__ __forceinline__ void accept(const PropInterval&, const double*, const double*, double, double, double) {}
+  __device__ __forceinline__ void arrive(int, const StepControl<Control>&, bool) {}
+};
+
+template <class M>
+__device__ __forceinline__ void sol_propagate(const PcSolPropagateArgs& A) {
+  PropDopri5<M> mth{A.p};
+  prop_walk<M>(A.p, mth);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -852,155 +868,95 @@ __device__ __forceinline__ void sol_propagate(const PcSolPropagateArgs& A) {
 // and the steps are pc_sol_propagate's to the bit.  No LDS, no atomics; the query cursor is bounded by Q.
 // ---------------------------------------------------------------------------------------------
 template <class M>
-__device__ __forceinline__ void sol_propagate_dense(const PcSolPropagateDenseArgs& A) {
-  using St = S<M>;
-  constexpr int NY = St::NY, NQ = St::NQ, NY1 = NY > 0 ? NY : 1, NQ1 = NQ > 0 ? NQ : 1;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= A.n_seg) return;
-  const int N = A.v.N;
-  const int64_t Q = A.Q;
-  const int32_t* sec_s = A.v.sec_s;
-  const int j0 = A.seg_node[i], j1 = A.seg_node[i + 1];
-  int k = A.seg_sec[i];
-  double t0, tF;
-  sol_times<M>(A.v, t0, tF);
-  const double stretch = 0.5 * (tF - t0);
-  const double nan = __builtin_nan("");
-  double v[St::NV > 0 ? St::NV : 1], y[NY1], ynew[NY1], I[NQ1], Inew[NQ1], Ks[7][NY1], Gs[7][NQ1];
-  sol_params<M>(A.v, v);
-  static_for<0, NY>([&](auto a_) {
-    constexpr int a = decltype(a_)::value;
-    y[a] = A.c.node_y[(int64_t)a * N + j0];
-    if (j0 == 0) A.y_arrive[(int64_t)a * N] = y[a];
-  });
-  static_for<0, NQ>([&](auto m_) {
-    constexpr int m = decltype(m_)::value;
-    I[m] = 0.0;
-    if (j0 == 0) A.q_arrive[(int64_t)m * N] = 0.0;
-  });
-  if (j0 == 0) {
-    A.accepted[0] = A.rejected[0] = 0;
-    for (int kq = A.node_q0[0]; kq < A.node_q0[1] && kq < Q; ++kq) {   // the queries at tau_0
-      const int64_t col = A.q_order[kq];
-      static_for<0, NY>([&](auto a_) { A.y_dense[(int64_t) decltype(a_)::value * Q + col] = y[decltype(a_)::value]; });
-      static_for<0, NQ>([&](auto m_) { A.q_dense[(int64_t) decltype(m_)::value * Q + col] = 0.0; });
-    }
-  }
-  int status = -1;
-  for (int j = j0; j < j1; ++j) {
-    int kq = A.node_q0[j + 1];
-    const int kq1 = A.node_q0[j + 2] < Q ? A.node_q0[j + 2] : (int)Q;
-    if (status < 0) {
-      if (j >= sec_s[k + 1] && k < A.v.K - 1) ++k;
-      const int sk = sec_s[k], n = sec_s[k + 1] - sk + 1;
-      const int64_t off = (int64_t)sk + k;
-      const double ta = A.c.sec_tau[k], w = A.c.sec_tau[k + 1] - ta;
-      const double ca = 2.0 * (A.tau[j] - ta) / w - 1.0, cb = 2.0 * (A.tau[j + 1] - ta) / w - 1.0;
-      const double g = stretch * (0.5 * w);
-      // the queries the step from c of width h to ce reaches (it has been accepted: ynew, Inew, Ks, Gs are its own)
-      auto answer = [&](double c, double h, double ce) {
-        while (kq < kq1) {
-          const double cq = 2.0 * (A.tau_q[kq] - ta) / w - 1.0;
-          if (!(cq <= ce)) break;
-          const int64_t col = A.q_order[kq];
-          if (cq == ce) {
-            static_for<0, NY>([&](auto a_) { A.y_dense[(int64_t) decltype(a_)::value * Q + col] = ynew[decltype(a_)::value]; });
-            static_for<0, NQ>([&](auto m_) { A.q_dense[(int64_t) decltype(m_)::value * Q + col] = Inew[decltype(m_)::value]; });
-          } else {
-            const double th = fmax((cq - c) / h, 0.0);
-            double b[7];
-            static_for<0, 7>([&](auto i_) {
-              constexpr int ii = decltype(i_)::value;
-              b[ii] = th * (dp_p(ii, 0) + th * (dp_p(ii, 1) + th * (dp_p(ii, 2) + th * dp_p(ii, 3))));
-            });
-            static_for<0, NY>([&](auto a_) {
-              constexpr int a = decltype(a_)::value;
-              double acc = 0.0;
-              static_for<0, 7>([&](auto i_) {
-                constexpr int ii = decltype(i_)::value;
-                if constexpr (dp_p_row(ii)) acc += Ks[ii][a] * b[ii];
-              });
-              A.y_dense[(int64_t)a * Q + col] = y[a] + h * acc;
-            });
-            static_for<0, NQ>([&](auto m_) {
-              constexpr int m = decltype(m_)::value;
-              double acc = 0.0;
-              static_for<0, 7>([&](auto i_) {
-                constexpr int ii = decltype(i_)::value;
-                if constexpr (dp_p_row(ii)) acc += Gs[ii][m] * b[ii];
-              });
-              A.q_dense[(int64_t)m * Q + col] = I[m] + h * acc;
-            });
-          }
-          ++kq;
-        }
-      };
-      auto advance = [&]() {
-        static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
-        static_for<0, NQ>([&](auto m_) { I[decltype(m_)::value] = Inew[decltype(m_)::value]; });
-      };
-      int n_acc = 0, n_rej = 0;
-      if (A.substeps > 0) {
-        const int m = A.substeps;
-        const double h = (cb - ca) / (double)m;
-        for (int q = 0; q < m; ++q) {
-          const double c = ca + (double)q * h;
-          const double hq = q == m - 1 ? cb - c : h, ce = q == m - 1 ? cb : c + h;
-          // the seventh stage only where a query falls into the step
-          const bool hit = kq < kq1 && 2.0 * (A.tau_q[kq] - ta) / w - 1.0 <= ce;
-          prop_stages<M, false, NQ>(A, v, y, I, off, n, c, hq, g, hit, Ks, Gs, ynew, Inew);
-          if (hit) answer(c, hq, ce);
-          advance();
-        }
-        n_acc = m;
-      } else {
-        double c = ca, h = cb - ca;
-        bool last = true, after_reject = false, done = false;
-        while (!done && n_acc + n_rej < A.max_steps) {
-          prop_stages<M, true, NQ>(A, v, y, I, off, n, c, h, g, true, Ks, Gs, ynew, Inew);
-          double err = 0.0;
-          bool bad = false;
-          prop_err<NY, NY1>(Ks, y, ynew, h, A.atol, A.rtol, err, bad);
-          if (A.integral_atol) prop_err<NQ, NQ1>(Gs, I, Inew, h, A.integral_atol, A.rtol, err, bad);
-          double factor = 0.2;
-          if (!bad) factor = err == 0.0 ? 5.0 : fmin(5.0, fmax(0.2, 0.9 * pow(err, -0.2)));
-          if (!bad && err <= 1.0) {
-            ++n_acc;
-            const double ce = last ? cb : c + h;
-            answer(c, h, ce);
-            advance();
-            c = ce;
-            if (after_reject) factor = fmin(factor, 1.0);
-            after_reject = false;
-            const double rest = cb - c;
-            if (last || !(rest > 0.0)) {
-              done = true;
-            } else {
-              h *= factor;
-              last = h >= rest;
-              if (last) h = rest;
-            }
-          } else {
-            ++n_rej;
-            h *= factor;
-            last = false;
-            after_reject = true;
-          }
-        }
-        if (!done) status = j;
-      }
-      A.accepted[j + 1] = n_acc;
-      A.rejected[j + 1] = n_rej;
-    } else {   // behind the interval that failed
-      A.accepted[j + 1] = A.rejected[j + 1] = 0;
-    }
-    static_for<0, NY>([&](auto a_) {
-      constexpr int a = decltype(a_)::value;
-      A.y_arrive[(int64_t)a * N + j + 1] = status >= 0 ? nan : y[a];
-    });
+struct PropDense {
+  using Control = StepDopri5;
+  static constexpr int NY = S<M>::NY, NQ = S<M>::NQ, NY1 = NY > 0 ? NY : 1, NQ1 = NQ > 0 ? NQ : 1;
+  const PcSolPropagateDenseArgs& A;
+  double I[NQ1], Inew[NQ1], Ks[7][NY1], Gs[7][NQ1];
+  int kq, kq1;   // the sorted queries of the interval that no step has answered yet
+  bool hit;      // a query falls into the attempt
+
+  __device__ __forceinline__ explicit PropDense(const PcSolPropagateDenseArgs& a) : A(a) {}
+  __device__ __forceinline__ void start(bool first, const double* y) {
+    const int N = A.p.v.N;
+    const int64_t Q = A.Q;
     static_for<0, NQ>([&](auto m_) {
       constexpr int m = decltype(m_)::value;
-      A.q_arrive[(int64_t)m * N + j + 1] = status >= 0 ? nan : I[m];
+      I[m] = 0.0;
+      if (first) A.q_arrive[(int64_t)m * N] = 0.0;
+    });
+    if (first)
+      for (int q = A.node_q0[0]; q < A.node_q0[1] && q < Q; ++q) {   // the queries at tau_0
+        const int64_t col = A.q_order[q];
+        static_for<0, NY>([&](auto a_) { A.y_dense[(int64_t) decltype(a_)::value * Q + col] = y[decltype(a_)::value]; });
+        static_for<0, NQ>([&](auto m_) { A.q_dense[(int64_t) decltype(m_)::value * Q + col] = 0.0; });
+      }
+  }
+  __device__ __forceinline__ void open(int j) {
+    kq = A.node_q0[j + 1];
+    kq1 = A.node_q0[j + 2] < A.Q ? A.node_q0[j + 2] : (int)A.Q;
+  }
+  template <bool FIXED>
+  __device__ __forceinline__ bool attempt(const PropInterval& iv, double* v, const double* y, double c, double h, double ce,
+                                          double* ynew, double& err, bool& bad) {
+    if constexpr (FIXED) {   // the seventh stage only where a query falls into the step
+      hit = kq < kq1 && 2.0 * (A.tau_q[kq] - iv.ta) / iv.w - 1.0 <= ce;
+      prop_stages<M, false, NQ>(A.p, v, y, I, iv.off, iv.n, c, h, iv.g, hit, Ks, Gs, ynew, Inew);
+    } else {
+      hit = true;
+      prop_stages<M, true, NQ>(A.p, v, y, I, iv.off, iv.n, c, h, iv.g, true, Ks, Gs, ynew, Inew);
+      prop_err<NY, NY1>(Ks, y, ynew, h, A.p.atol, A.p.rtol, err, bad);
+      if (A.integral_atol) prop_err<NQ, NQ1>(Gs, I, Inew, h, A.integral_atol, A.p.rtol, err, bad);
+    }
+    return true;
+  }
+  // the queries the step from c of width h to ce reaches (ynew, Inew, Ks, Gs are its own), then the integrals advance
+  __device__ __forceinline__ void accept(const PropInterval& iv, const double* y, const double* ynew, double c, double h, double ce) {
+    const int64_t Q = A.Q;
+    while (hit && kq < kq1) {
+      const double cq = 2.0 * (A.tau_q[kq] - iv.ta) / iv.w - 1.0;
+      if (!(cq <= ce)) break;
+      const int64_t col = A.q_order[kq];
+      if (cq == ce) {
+        static_for<0, NY>([&](auto a_) { A.y_dense[(int64_t) decltype(a_)::value * Q + col] = ynew[decltype(a_)::value]; });
+        static_for<0, NQ>([&](auto m_) { A.q_dense[(int64_t) decltype(m_)::value * Q + col] = Inew[decltype(m_)::value]; });
+      } else {
+        const double th = fmax((cq - c) / h, 0.0);
+        double b[7];
+        static_for<0, 7>([&](auto i_) {
+          constexpr int ii = decltype(i_)::value;
+          b[ii] = th * (dp_p(ii, 0) + th * (dp_p(ii, 1) + th * (dp_p(ii, 2) + th * dp_p(ii, 3))));
+        });
+        static_for<0, NY>([&](auto a_) {
+          constexpr int a = decltype(a_)::value;
+          double acc = 0.0;
+          static_for<0, 7>([&](auto i_) {
+            constexpr int ii = decltype(i_)::value;
+            if constexpr (dp_p_row(ii)) acc += Ks[ii][a] * b[ii];
+          });
+          A.y_dense[(int64_t)a * Q + col] = y[a] + h * acc;
+        });
+        static_for<0, NQ>([&](auto m_) {
+          constexpr int m = decltype(m_)::value;
+          double acc = 0.0;
+          static_for<0, 7>([&](auto i_) {
+            constexpr int ii = decltype(i_)::value;
+            if constexpr (dp_p_row(ii)) acc += Gs[ii][m] * b[ii];
+          });
+          A.q_dense[(int64_t)m * Q + col] = I[m] + h * acc;
+        });
+      }
+      ++kq;
+    }
+    static_for<0, NQ>([&](auto m_) { I[decltype(m_)::value] = Inew[decltype(m_)::value]; });
+  }
+  __device__ __forceinline__ void arrive(int j, const StepControl<Control>&, bool failed) {
+    const int N = A.p.v.N;
+    const int64_t Q = A.Q;
+    const double nan = __builtin_nan("");
+    static_for<0, NQ>([&](auto m_) {
+      constexpr int m = decltype(m_)::value;
+      A.q_arrive[(int64_t)m * N + j + 1] = failed ? nan : I[m];
     });
     for (; kq < kq1; ++kq) {   // the queries no accepted step has reached: behind the failure
       const int64_t col = A.q_order[kq];
@@ -1008,7 +964,12 @@ __device__ __forceinline__ void sol_propagate_dense(const PcSolPropagateDenseArg
       static_for<0, NQ>([&](auto m_) { A.q_dense[(int64_t) decltype(m_)::value * Q + col] = nan; });
     }
   }
-  A.seg_status[i] = status;
+};
+
+template <class M>
+__device__ __forceinline__ void sol_propagate_dense(const PcSolPropagateDenseArgs& A) {
+  PropDense<M> mth(A);
+  prop_walk<M>(A.p, mth);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1248,7 +1209,7 @@ __device__ __forceinline__ bool stiff_step(const PcSolPropagateStiffArgs& A, dou
     static_for<0, NY>([&](auto a_) { v[decltype(a_)::value] = y[decltype(a_)::value]; });
     static_for<0, NU>([&](auto b_) {
       constexpr int b = decltype(b_)::value;
-      v[NY + b] = sol_legendre(A.c.coef_u + (int64_t)b * A.c.NC + off, n, c);
+      v[NY + b] = sol_legendre(A.p.c.coef_u + (int64_t)b * A.p.c.NC + off, n, c);
     });
     M::eval_fj(v, F, Jv);
     static_for<0, NY>([&](auto a_) { Kc[decltype(a_)::value] = g * F[decltype(a_)::value]; });
@@ -1267,7 +1228,7 @@ __device__ __forceinline__ bool stiff_step(const PcSolPropagateStiffArgs& A, dou
     // (no branch around a stage: a failed stage leaves the Newton loops of the later ones empty)
     static_for<0, NU>([&](auto b_) {
       constexpr int b = decltype(b_)::value;
-      v[NY + b] = sol_legendre(A.c.coef_u + (int64_t)b * A.c.NC + off, n, c + sd_c(s) * h);
+      v[NY + b] = sol_legendre(A.p.c.coef_u + (int64_t)b * A.p.c.NC + off, n, c + sd_c(s) * h);
     });
     double base[NY1];   // sum_{l<s} a_sl K_l, l ascending, zero entries of the tableau left out
     static_for<0, NY>([&](auto a_) {
@@ -1295,7 +1256,7 @@ __device__ __forceinline__ bool stiff_step(const PcSolPropagateStiffArgs& A, dou
       static_for<0, NY>([&](auto a_) {
         constexpr int a = decltype(a_)::value;
         Kc[a] += r[a];
-        const double q = fabs(hg * r[a]) / (A.atol[a] + A.rtol * fmax(fabs(y[a]), fabs(v[a])));
+        const double q = fabs(hg * r[a]) / (A.p.atol[a] + A.p.rtol * fmax(fabs(y[a]), fabs(v[a])));
         if (!(q <= 1.7976931348623157e308)) ok = false;   // NaN or inf (fmax would drop a NaN)
         theta = fmax(theta, q);
       });
@@ -1323,13 +1284,16 @@ __device__ __forceinline__ bool stiff_step(const PcSolPropagateStiffArgs& A, dou
   bad = false;
   static_for<0, NY>([&](auto a_) {
     constexpr int a = decltype(a_)::value;
-    const double q = fabs(e[a]) / (A.atol[a] + A.rtol * fmax(fabs(y[a]), fabs(ynew[a])));
+    const double q = fabs(e[a]) / (A.p.atol[a] + A.p.rtol * fmax(fabs(y[a]), fabs(ynew[a])));
     if (!(q <= 1.7976931348623157e308)) bad = true;
     err = fmax(err, q);
   });
   return true;
 }
 
+// (This kernel is not yet a method of prop_walk: as one, it took two more VGPRs on many models and lost a wave per SIMD
+// on the tumour and the double-pendulum models, and what kept the pair live was not found.  Its walk and its step
+// control below are pc_sol_propagate's, restated; StepControl<StepSdirk4> states the same control and is tested.)
 template <class M>
 __device__ __forceinline__ void sol_propagate_stiff(const PcSolPropagateStiffArgs& A) {
   using St = S<M>;
@@ -1339,44 +1303,44 @@ __device__ __forceinline__ void sol_propagate_stiff(const PcSolPropagateStiffArg
     __shared__ int32_t piv[NY1 * PC_SOL_PROP_TB];
     const int lane = threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= A.n_seg || lane >= PC_SOL_PROP_TB) return;
-    const int N = A.v.N;
-    const int32_t* sec_s = A.v.sec_s;
-    const int j0 = A.seg_node[i], j1 = A.seg_node[i + 1];
-    int k = A.seg_sec[i];
+    if (i >= A.p.n_seg || lane >= PC_SOL_PROP_TB) return;
+    const int N = A.p.v.N;
+    const int32_t* sec_s = A.p.v.sec_s;
+    const int j0 = A.p.seg_node[i], j1 = A.p.seg_node[i + 1];
+    int k = A.p.seg_sec[i];
     double t0, tF;
-    sol_times<M>(A.v, t0, tF);
+    sol_times<M>(A.p.v, t0, tF);
     const double stretch = 0.5 * (tF - t0);
     double v[St::NV > 0 ? St::NV : 1], y[NY1], ynew[NY1];
-    sol_params<M>(A.v, v);
+    sol_params<M>(A.p.v, v);
     static_for<0, NY>([&](auto a_) {
       constexpr int a = decltype(a_)::value;
-      y[a] = A.c.node_y[(int64_t)a * N + j0];
-      if (j0 == 0) A.y_arrive[(int64_t)a * N] = y[a];
+      y[a] = A.p.c.node_y[(int64_t)a * N + j0];
+      if (j0 == 0) A.p.y_arrive[(int64_t)a * N] = y[a];
     });
-    if (j0 == 0) A.accepted[0] = A.rejected[0] = A.newton_rejected[0] = A.newton_iterations[0] = 0;
-    const bool fixed = A.substeps > 0;
+    if (j0 == 0) A.p.accepted[0] = A.p.rejected[0] = A.newton_rejected[0] = A.newton_iterations[0] = 0;
+    const bool fixed = A.p.substeps > 0;
     int status = -1;
     for (int j = j0; j < j1; ++j) {
       if (status >= 0) {   // behind the interval that failed
-        static_for<0, NY>([&](auto a_) { A.y_arrive[(int64_t) decltype(a_)::value * N + j + 1] = __builtin_nan(""); });
-        A.accepted[j + 1] = A.rejected[j + 1] = A.newton_rejected[j + 1] = A.newton_iterations[j + 1] = 0;
+        static_for<0, NY>([&](auto a_) { A.p.y_arrive[(int64_t) decltype(a_)::value * N + j + 1] = __builtin_nan(""); });
+        A.p.accepted[j + 1] = A.p.rejected[j + 1] = A.newton_rejected[j + 1] = A.newton_iterations[j + 1] = 0;
         continue;
       }
-      if (j >= sec_s[k + 1] && k < A.v.K - 1) ++k;
+      if (j >= sec_s[k + 1] && k < A.p.v.K - 1) ++k;
       const int sk = sec_s[k], n = sec_s[k + 1] - sk + 1;
       const int64_t off = (int64_t)sk + k;
-      const double ta = A.c.sec_tau[k], w = A.c.sec_tau[k + 1] - ta;
-      const double ca = 2.0 * (A.tau[j] - ta) / w - 1.0, cb = 2.0 * (A.tau[j + 1] - ta) / w - 1.0;
+      const double ta = A.p.c.sec_tau[k], w = A.p.c.sec_tau[k + 1] - ta;
+      const double ca = 2.0 * (A.p.tau[j] - ta) / w - 1.0, cb = 2.0 * (A.p.tau[j + 1] - ta) / w - 1.0;
       const double g = stretch * (0.5 * w);
       int n_acc = 0, n_rej = 0, n_newt = 0, iters = 0;
-      const double h0 = fixed ? (cb - ca) / (double)A.substeps : cb - ca;
+      const double h0 = fixed ? (cb - ca) / (double)A.p.substeps : cb - ca;
       double c = ca, h = h0;
       bool last = true, after_reject = false, done = false;
-      while (!done && (fixed || n_acc + n_rej < A.max_steps)) {
+      while (!done && (fixed || n_acc + n_rej < A.p.max_steps)) {
         if (fixed) {   // step q starts at ca + q h0 (computed, not accumulated); the last one ends at cb
           c = ca + (double)n_acc * h0;
-          h = n_acc == A.substeps - 1 ? cb - c : h0;
+          h = n_acc == A.p.substeps - 1 ? cb - c : h0;
         }
         double err = 0.0;
         bool bad = false;
@@ -1389,7 +1353,7 @@ __device__ __forceinline__ void sol_propagate_stiff(const PcSolPropagateStiffArg
           }
           ++n_acc;
           static_for<0, NY>([&](auto a_) { y[decltype(a_)::value] = ynew[decltype(a_)::value]; });
-          done = n_acc == A.substeps;
+          done = n_acc == A.p.substeps;
           continue;
         }
         double factor = newton ? 0.2 : 0.25;
@@ -1417,16 +1381,16 @@ __device__ __forceinline__ void sol_propagate_stiff(const PcSolPropagateStiffArg
         }
       }
       if (!done) status = j;
-      A.accepted[j + 1] = n_acc;
-      A.rejected[j + 1] = n_rej;
+      A.p.accepted[j + 1] = n_acc;
+      A.p.rejected[j + 1] = n_rej;
       A.newton_rejected[j + 1] = n_newt;
       A.newton_iterations[j + 1] = iters;
       static_for<0, NY>([&](auto a_) {
         constexpr int a = decltype(a_)::value;
-        A.y_arrive[(int64_t)a * N + j + 1] = status >= 0 ? __builtin_nan("") : y[a];
+        A.p.y_arrive[(int64_t)a * N + j + 1] = status >= 0 ? __builtin_nan("") : y[a];
       });
     }
-    A.seg_status[i] = status;
+    A.p.seg_status[i] = status;
   }
 }
 #undef PC_SD_LU

@@ -11,9 +11,10 @@
 // Costates (pc_solution_set_multipliers): the index arithmetic is pc_costate_plan.hpp.  The multipliers belong to the
 // constraint and objective scaling the handle holds when they are set, which are read then.
 //
-// Propagation (pc_solution_propagate): the index arithmetic is pc_propagate_plan.hpp.  The segment list, the first
-// sections and atol are staged in buffers the solution keeps, so a device call may return before the kernel has run.
-// pc_solution_propagate_dense stages its own lists the same way, and with them integral_atol and the sorted queries.
+// Propagation (pc_solution_propagate, _dense, _stiff): the index arithmetic is pc_propagate_plan.hpp.  The segment list,
+// the first sections and atol are staged in buffers the solution keeps, so a device call may return before the kernel
+// has run; the three kernels share them, as every launch waits for the stream before it uploads
+// (solution_stage_propagate).  pc_solution_propagate_dense stages integral_atol and the sorted queries the same way.
 //
 // Path and bound multipliers (pc_solution_set_bound_multipliers): the index arithmetic is pc_optimality_plan.hpp.  The
 // solution keeps its own device copy of the constraint multipliers, the tables and the scaling they were set under, so
@@ -42,10 +43,10 @@ struct pc_solution {
     DevBuf<double> node_mu, node_zeta, end_z, node_Hz, coef_mu, coef_zeta;   // by pc_solution_set_bound_multipliers
     hipFunction_t fn_sample_optimality = nullptr;
     PcPhaseView view_w;     // view with the constraint scaling the multipliers were set under
-    DevBuf<int32_t> prop_seg, prop_sec;          // propagation: the staged segment list and first sections,
-    DevBuf<double> prop_atol;                    // and atol
-    DevBuf<int32_t> dense_seg, dense_sec, dense_order, dense_q0;   // dense propagation: its own staged lists,
-    DevBuf<double> dense_atol, dense_iatol, dense_tau_q;           // tolerances and sorted queries
+    DevBuf<int32_t> prop_seg, prop_sec;          // propagation, all three kernels: the staged segment list and first
+    DevBuf<double> prop_atol;                    // sections, and atol
+    DevBuf<int32_t> dense_order, dense_q0;       // dense propagation besides: the sorted queries, their order and slots,
+    DevBuf<double> dense_iatol, dense_tau_q;     // and integral_atol
     std::vector<double> h_tau;                   // the node abscissae on the host (the queries' slots are found in them)
     hipFunction_t fn_sample = nullptr, fn_sample_costate = nullptr, fn_propagate = nullptr, fn_propagate_dense = nullptr,
                   fn_propagate_stiff = nullptr;
@@ -362,6 +363,40 @@ pc_solution::Phase& solution_phase(pc_solution* s, int phase) {
   return *s->ph[phase];
 }
 
+// The four outputs every propagation kernel has
+struct PropOutputs {
+  double* y;
+  int32_t *acc, *rej, *status;
+};
+
+// What the three propagation launches share once their checks are through and the plan P is made: the kernel (found
+// once), the wait for the stream (an earlier call may still read the staged lists), the staged lists and the prefix of
+// the argument block.
+void solution_stage_propagate(pc_solution* s, int phase, const pcs::PropagatePlan& P, hipFunction_t* fn, const char* kernel,
+                              int64_t substeps, double rtol, const double* atol, int64_t max_steps, const PropOutputs& o,
+                              PcSolPropCommon& p) {
+  auto& S = *s->ph[phase];
+  if (!*fn) HIP_OK(find_fn(s->h, fn, (kernel + std::to_string(phase)).c_str()));
+  HIP_OK(hipStreamSynchronize(s->h->stream));
+  S.prop_seg.upload(P.seg_node);
+  S.prop_sec.upload(P.seg_sec);
+  S.prop_atol.upload(std::vector<double>(atol, atol + S.NY));
+  p.v = S.view;
+  p.c = S.curves;
+  p.tau = S.node_tau.p;
+  p.seg_node = S.prop_seg.p;
+  p.seg_sec = S.prop_sec.p;
+  p.atol = S.prop_atol.p;
+  p.y_arrive = o.y;
+  p.accepted = o.acc;
+  p.rejected = o.rej;
+  p.seg_status = o.status;
+  p.rtol = rtol;
+  p.n_seg = P.n_seg;
+  p.substeps = (int32_t)substeps;
+  p.max_steps = (int32_t)max_steps;
+}
+
 // pc_sol_propagate_p<phase> on the handle's stream; the outputs are device arrays ([n_y][N], [N], [N], [n_seg])
 void solution_launch_propagate(pc_solution* s, int phase, int64_t n_seg, const int32_t* seg_nodes, int64_t substeps, double rtol,
                                const double* atol, int64_t max_steps, double* d_y, int32_t* d_acc, int32_t* d_rej, int32_t* d_status) {
@@ -369,27 +404,10 @@ void solution_launch_propagate(pc_solution* s, int phase, int64_t n_seg, const i
   pcs::check_propagate_tolerances(substeps, rtol, atol, S.NY, max_steps);
   const pcs::PropagatePlan P = pcs::build_propagate_plan(S.plan, n_seg, seg_nodes);
   if (!d_acc || !d_rej || !d_status || (S.NY > 0 && !d_y)) throw std::runtime_error("propagate: null output");
-  if (!S.fn_propagate) HIP_OK(find_fn(s->h, &S.fn_propagate, ("pc_sol_propagate_p" + std::to_string(phase)).c_str()));
-  HIP_OK(hipStreamSynchronize(s->h->stream));   // an earlier call may still read the staged lists
-  S.prop_seg.upload(P.seg_node);
-  S.prop_sec.upload(P.seg_sec);
-  S.prop_atol.upload(std::vector<double>(atol, atol + S.NY));
   PcSolPropagateArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.v = S.view;
-  a.c = S.curves;
-  a.tau = S.node_tau.p;
-  a.seg_node = S.prop_seg.p;
-  a.seg_sec = S.prop_sec.p;
-  a.atol = S.prop_atol.p;
-  a.y_arrive = d_y;
-  a.accepted = d_acc;
-  a.rejected = d_rej;
-  a.seg_status = d_status;
-  a.rtol = rtol;
-  a.n_seg = P.n_seg;
-  a.substeps = (int32_t)substeps;
-  a.max_steps = (int32_t)max_steps;
+  solution_stage_propagate(s, phase, P, &S.fn_propagate, "pc_sol_propagate_p", substeps, rtol, atol, max_steps,
+                           {d_y, d_acc, d_rej, d_status}, a.p);
   launch_block(S.fn_propagate, (unsigned)P.blocks, (unsigned)P.TB, 0, s->h->stream, a);
 }
 
@@ -404,30 +422,12 @@ void solution_launch_propagate_stiff(pc_solution* s, int phase, int64_t n_seg, c
   const pcs::PropagatePlan P = pcs::build_propagate_plan(S.plan, n_seg, seg_nodes);
   if (!d_acc || !d_rej || !d_status || !d_newton_rej || !d_newton_it || (S.NY > 0 && !d_y))
     throw std::runtime_error("propagate: null output");
-  if (!S.fn_propagate_stiff)
-    HIP_OK(find_fn(s->h, &S.fn_propagate_stiff, ("pc_sol_propagate_stiff_p" + std::to_string(phase)).c_str()));
-  HIP_OK(hipStreamSynchronize(s->h->stream));   // an earlier call may still read the staged lists
-  S.prop_seg.upload(P.seg_node);
-  S.prop_sec.upload(P.seg_sec);
-  S.prop_atol.upload(std::vector<double>(atol, atol + S.NY));
   PcSolPropagateStiffArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.v = S.view;
-  a.c = S.curves;
-  a.tau = S.node_tau.p;
-  a.seg_node = S.prop_seg.p;
-  a.seg_sec = S.prop_sec.p;
-  a.atol = S.prop_atol.p;
-  a.y_arrive = d_y;
-  a.accepted = d_acc;
-  a.rejected = d_rej;
-  a.seg_status = d_status;
+  solution_stage_propagate(s, phase, P, &S.fn_propagate_stiff, "pc_sol_propagate_stiff_p", substeps, rtol, atol, max_steps,
+                           {d_y, d_acc, d_rej, d_status}, a.p);
   a.newton_rejected = d_newton_rej;
   a.newton_iterations = d_newton_it;
-  a.rtol = rtol;
-  a.n_seg = P.n_seg;
-  a.substeps = (int32_t)substeps;
-  a.max_steps = (int32_t)max_steps;
   a.newton_max = (int32_t)newton_max;
   launch_block(S.fn_propagate_stiff, (unsigned)P.blocks, (unsigned)P.TB, 0, s->h->stream, a);
 }
@@ -446,40 +446,22 @@ void solution_launch_propagate_dense(pc_solution* s, int phase, int64_t n_seg, c
   if (!d_acc || !d_rej || !d_status || (S.NY > 0 && !d_y) || (S.NQ > 0 && !d_q) ||
       (D.Q > 0 && ((S.NY > 0 && !d_yd) || (S.NQ > 0 && !d_qd))))
     throw std::runtime_error("propagate: null output");
-  if (!S.fn_propagate_dense)
-    HIP_OK(find_fn(s->h, &S.fn_propagate_dense, ("pc_sol_propagate_dense_p" + std::to_string(phase)).c_str()));
-  HIP_OK(hipStreamSynchronize(s->h->stream));   // an earlier call may still read the staged lists
-  S.dense_seg.upload(P.seg_node);
-  S.dense_sec.upload(P.seg_sec);
-  S.dense_atol.upload(std::vector<double>(atol, atol + S.NY));
+  PcSolPropagateDenseArgs a;
+  std::memset(&a, 0, sizeof(a));
+  solution_stage_propagate(s, phase, P, &S.fn_propagate_dense, "pc_sol_propagate_dense_p", substeps, rtol, atol, max_steps,
+                           {d_y, d_acc, d_rej, d_status}, a.p);
   if (integral_atol) S.dense_iatol.upload(std::vector<double>(integral_atol, integral_atol + S.NQ));
   S.dense_tau_q.upload(D.tau_sorted);
   S.dense_order.upload(D.q_order);
   S.dense_q0.upload(D.node_q0);
-  PcSolPropagateDenseArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.v = S.view;
-  a.c = S.curves;
-  a.tau = S.node_tau.p;
-  a.seg_node = S.dense_seg.p;
-  a.seg_sec = S.dense_sec.p;
-  a.atol = S.dense_atol.p;
   a.integral_atol = integral_atol && S.NQ > 0 ? S.dense_iatol.p : nullptr;
   a.tau_q = S.dense_tau_q.p;
   a.q_order = S.dense_order.p;
   a.node_q0 = S.dense_q0.p;
-  a.y_arrive = d_y;
-  a.accepted = d_acc;
-  a.rejected = d_rej;
-  a.seg_status = d_status;
   a.q_arrive = d_q;
   a.y_dense = d_yd;
   a.q_dense = d_qd;
-  a.rtol = rtol;
   a.Q = D.Q;
-  a.n_seg = P.n_seg;
-  a.substeps = (int32_t)substeps;
-  a.max_steps = (int32_t)max_steps;
   launch_block(S.fn_propagate_dense, (unsigned)P.blocks, (unsigned)P.TB, 0, s->h->stream, a);
 }
 
@@ -491,6 +473,31 @@ pc_solution::Phase& solution_costate_phase(pc_solution* s, int phase) {
 
 void solution_down(double* dst, const DevBuf<double>& src, size_t count) {
   if (dst && count) HIP_OK(hipMemcpy(dst, src.p, count * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+void check_segment_count(const pc_solution::Phase& S, int64_t n_seg) {
+  if (n_seg < 1 || n_seg > (int64_t)S.plan.N - 1) throw std::runtime_error("propagate: the number of segments must be in [1, N - 1]");
+}
+
+// The host-pointer variant of a propagation call, behind the caller's checks: the device arrays of the four outputs every
+// method has, launch (on them and on the caller's further arrays), the wait for the stream and the copies down of the
+// four.  The caller copies its further outputs down behind it.
+template <class Launch>
+void solution_propagate_to_host(pc_solution* sol, pc_solution::Phase& S, int64_t n_seg, double* y_arrive, int32_t* accepted,
+                                int32_t* rejected, int32_t* seg_status, Launch launch) {
+  const size_t N = (size_t)S.plan.N;
+  DevBuf<double> d_y;
+  DevBuf<int32_t> d_acc, d_rej, d_st;
+  d_y.alloc(N * (size_t)std::max(1, S.NY));
+  d_acc.alloc(N);
+  d_rej.alloc(N);
+  d_st.alloc((size_t)n_seg);
+  launch(d_y.p, d_acc.p, d_rej.p, d_st.p);
+  HIP_OK(hipStreamSynchronize(sol->h->stream));
+  solution_down(y_arrive, d_y, N * S.NY);
+  HIP_OK(hipMemcpy(accepted, d_acc.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(rejected, d_rej.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(seg_status, d_st.p, (size_t)n_seg * sizeof(int32_t), hipMemcpyDeviceToHost));
 }
 
 pc_solution::Phase& solution_optimality_phase(pc_solution* s, int phase) {
@@ -726,20 +733,12 @@ int pc_solution_propagate(pc_solution* sol, int phase, int64_t n_seg, const int3
   return guarded(g_err, [&] {
     auto& S = solution_phase(sol, phase);
     if (!accepted || !rejected || !seg_status || (S.NY > 0 && !y_arrive)) throw std::runtime_error("propagate: null output");
-    if (n_seg < 1 || n_seg > (int64_t)S.plan.N - 1) throw std::runtime_error("propagate: the number of segments must be in [1, N - 1]");
-    const size_t N = (size_t)S.plan.N;
-    DevBuf<double> d_y;
-    DevBuf<int32_t> d_acc, d_rej, d_st;
-    d_y.alloc(N * (size_t)std::max(1, S.NY));
-    d_acc.alloc(N);
-    d_rej.alloc(N);
-    d_st.alloc((size_t)n_seg);
-    solution_launch_propagate(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, d_y.p, d_acc.p, d_rej.p, d_st.p);
-    HIP_OK(hipStreamSynchronize(sol->h->stream));
-    solution_down(y_arrive, d_y, N * S.NY);
-    HIP_OK(hipMemcpy(accepted, d_acc.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(rejected, d_rej.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(seg_status, d_st.p, (size_t)n_seg * sizeof(int32_t), hipMemcpyDeviceToHost));
+    check_segment_count(S, n_seg);
+    solution_propagate_to_host(sol, S, n_seg, y_arrive, accepted, rejected, seg_status,
+                               [&](double* d_y, int32_t* d_acc, int32_t* d_rej, int32_t* d_st) {
+                                 solution_launch_propagate(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, d_y, d_acc,
+                                                           d_rej, d_st);
+                               });
   });
 }
 
@@ -760,25 +759,18 @@ int pc_solution_propagate_stiff(pc_solution* sol, int phase, int64_t n_seg, cons
     auto& S = solution_phase(sol, phase);
     if (!accepted || !rejected || !seg_status || !newton_rejected || !newton_iterations || (S.NY > 0 && !y_arrive))
       throw std::runtime_error("propagate: null output");
-    if (n_seg < 1 || n_seg > (int64_t)S.plan.N - 1) throw std::runtime_error("propagate: the number of segments must be in [1, N - 1]");
+    check_segment_count(S, n_seg);
     const size_t N = (size_t)S.plan.N;
-    DevBuf<double> d_y;
-    DevBuf<int32_t> d_acc, d_rej, d_st, d_nr, d_ni;
-    d_y.alloc(N * (size_t)std::max(1, S.NY));
-    d_acc.alloc(N);
-    d_rej.alloc(N);
+    DevBuf<int32_t> d_nr, d_ni;
     d_nr.alloc(N);
     d_ni.alloc(N);
-    d_st.alloc((size_t)n_seg);
-    solution_launch_propagate_stiff(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps, newton_max, d_y.p, d_acc.p,
-                                    d_rej.p, d_st.p, d_nr.p, d_ni.p);
-    HIP_OK(hipStreamSynchronize(sol->h->stream));
-    solution_down(y_arrive, d_y, N * S.NY);
-    HIP_OK(hipMemcpy(accepted, d_acc.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(rejected, d_rej.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    solution_propagate_to_host(sol, S, n_seg, y_arrive, accepted, rejected, seg_status,
+                               [&](double* d_y, int32_t* d_acc, int32_t* d_rej, int32_t* d_st) {
+                                 solution_launch_propagate_stiff(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, max_steps,
+                                                                 newton_max, d_y, d_acc, d_rej, d_st, d_nr.p, d_ni.p);
+                               });
     HIP_OK(hipMemcpy(newton_rejected, d_nr.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(newton_iterations, d_ni.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(seg_status, d_st.p, (size_t)n_seg * sizeof(int32_t), hipMemcpyDeviceToHost));
   });
 }
 
@@ -802,28 +794,22 @@ int pc_solution_propagate_dense(pc_solution* sol, int phase, int64_t n_seg, cons
     if (!accepted || !rejected || !seg_status || (S.NY > 0 && !y_arrive) || (S.NQ > 0 && !q_arrive) ||
         (n_query > 0 && ((S.NY > 0 && !y_dense) || (S.NQ > 0 && !q_dense))))
       throw std::runtime_error("propagate: null output");
-    if (n_seg < 1 || n_seg > (int64_t)S.plan.N - 1) throw std::runtime_error("propagate: the number of segments must be in [1, N - 1]");
+    check_segment_count(S, n_seg);
     if (n_query < 0 || n_query > (int64_t)INT32_MAX) throw std::runtime_error("propagate: the number of queries must be in [0, 2^31)");
     const size_t N = (size_t)S.plan.N, Qn = (size_t)n_query;
-    DevBuf<double> d_y, d_q, d_yd, d_qd;
-    DevBuf<int32_t> d_acc, d_rej, d_st;
-    d_y.alloc(N * (size_t)std::max(1, S.NY));
+    DevBuf<double> d_q, d_yd, d_qd;
     d_q.alloc(N * (size_t)std::max(1, S.NQ));
     d_yd.alloc(Qn * (size_t)S.NY);
     d_qd.alloc(Qn * (size_t)S.NQ);
-    d_acc.alloc(N);
-    d_rej.alloc(N);
-    d_st.alloc((size_t)n_seg);
-    solution_launch_propagate_dense(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, integral_atol, max_steps, n_query, tau_q,
-                                    d_y.p, d_acc.p, d_rej.p, d_st.p, d_q.p, d_yd.p, d_qd.p);
-    HIP_OK(hipStreamSynchronize(sol->h->stream));
-    solution_down(y_arrive, d_y, N * S.NY);
+    solution_propagate_to_host(sol, S, n_seg, y_arrive, accepted, rejected, seg_status,
+                               [&](double* d_y, int32_t* d_acc, int32_t* d_rej, int32_t* d_st) {
+                                 solution_launch_propagate_dense(sol, phase, n_seg, seg_nodes, substeps, rtol, atol, integral_atol,
+                                                                 max_steps, n_query, tau_q, d_y, d_acc, d_rej, d_st, d_q.p, d_yd.p,
+                                                                 d_qd.p);
+                               });
     solution_down(q_arrive, d_q, N * S.NQ);
     solution_down(y_dense, d_yd, Qn * S.NY);
     solution_down(q_dense, d_qd, Qn * S.NQ);
-    HIP_OK(hipMemcpy(accepted, d_acc.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(rejected, d_rej.p, N * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(seg_status, d_st.p, (size_t)n_seg * sizeof(int32_t), hipMemcpyDeviceToHost));
   });
 }
 

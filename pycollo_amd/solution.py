@@ -902,6 +902,34 @@ class Solution:
         V = self.engine.layout.expand_x(self.engine.V_ocp)
         return np.array([V[pl.x_off + a * pl.N] for a in range(pl.n_y)], dtype=np.float64)
 
+    def _propagate_prelude(self, phase, restart, rtol, atol, substeps, max_steps, maybe_device):
+        """What :meth:`propagate` and :meth:`propagate_dense` do first: the segment list, ``atol`` (its default, its
+        broadcast, its checks with the other tolerances) and where the outputs go -- the device of the first torch
+        device tensor among ``maybe_device``, else ``None`` for NumPy.  Returns seg, at, V, device, n_seg, m."""
+        pl, mesh = self.engine.layout.phases[phase], self.engine.meshes[phase]
+        device = next((a.device for a in maybe_device if _is_torch(a) and a.is_cuda), None)
+        seg = propagation_segments(restart, mesh.s, pl.N)
+        V = self.state_scale(phase)
+        if atol is None:
+            at = float(rtol) * V
+        else:
+            if _is_torch(atol):
+                atol = atol.detach().cpu().numpy()
+            at = np.ascontiguousarray(np.broadcast_to(np.asarray(atol, dtype=np.float64), (pl.n_y,)))
+        check_propagate_tolerances(substeps, rtol, at, max_steps)
+        return seg, np.ascontiguousarray(at, dtype=np.float64), V, device, len(seg) - 1, 0 if substeps is None else int(substeps)
+
+    def _propagation_fields(self, phase, y, status, V, device):
+        """What :class:`Propagation` and :class:`DensePropagation` derive from the arrivals ``y`` and ``status``, as
+        NumPy arrays or as torch tensors on ``device``: defect, relative_defect, ok, terminal_defect."""
+        node_y = np.asarray(self.state[phase], dtype=np.float64).reshape(y.shape)
+        scale = V[:, None]
+        if device is not None:
+            import torch
+            node_y, scale = torch.as_tensor(node_y, device=device), torch.as_tensor(V, device=device)[:, None]
+        defect = y - node_y
+        return dict(defect=defect, relative_defect=defect / scale, ok=status == -1, terminal_defect=defect[:, -1])
+
     def propagate(self, phase: int, *, restart="nodes", rtol: float = 1e-9, atol=None, substeps=None, max_steps: int = 4096,
                   method: str = "dopri5", newton_max: int = 8):
         """Integrate the dynamics forward under the solution's controls (``pc_sol_propagate_p<i>``) and
@@ -932,23 +960,12 @@ class Solution:
         NumPy out, unless ``restart`` or ``atol`` is a torch device tensor: then torch tensors on that device.  Bad
         arguments raise ``ValueError`` before anything is launched."""
         phase = self._phase(phase, need_handle=False)
-        pl, mesh = self.engine.layout.phases[phase], self.engine.meshes[phase]
+        pl = self.engine.layout.phases[phase]
         N, n_y = pl.N, pl.n_y
-        device = next((a.device for a in (restart, atol) if _is_torch(a) and a.is_cuda), None)
-        seg = propagation_segments(restart, mesh.s, N)
-        V = self.state_scale(phase)
-        if atol is None:
-            at = float(rtol) * V
-        else:
-            if _is_torch(atol):
-                atol = atol.detach().cpu().numpy()
-            at = np.ascontiguousarray(np.broadcast_to(np.asarray(atol, dtype=np.float64), (n_y,)))
-        check_propagate_tolerances(substeps, rtol, at, max_steps)
+        seg, at, V, device, n_seg, m = self._propagate_prelude(phase, restart, rtol, atol, substeps, max_steps, (restart, atol))
         check_propagate_method(method, newton_max, rtol, n_y)
         stiff = method == "sdirk4"
-        at = np.ascontiguousarray(at, dtype=np.float64)
         self._phase(phase)     # (the device is needed from here on)
-        n_seg, m = len(seg) - 1, 0 if substeps is None else int(substeps)
         head = (self._h, phase, n_seg, seg.ctypes.data, m, float(rtol), at.ctypes.data if n_y else None, int(max_steps))
         if stiff:
             head += (int(newton_max),)
@@ -968,8 +985,6 @@ class Solution:
                 self._check(self._lib.pc_solution_propagate_device(*head, y.data_ptr() if n_y else None, acc.data_ptr(),
                                                                    rej.data_ptr(), status.data_ptr()))
             self._check(self._lib.pc_synchronize(self.engine._h))
-            node_y = torch.as_tensor(np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N), device=device)
-            scale = torch.as_tensor(V, device=device)[:, None]
         else:
             y = np.empty((n_y, N))
             acc, rej, status = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32), np.empty(n_seg, dtype=np.int32)
@@ -981,12 +996,8 @@ class Solution:
             else:
                 self._check(self._lib.pc_solution_propagate(*head, y.ctypes.data if n_y else None, acc.ctypes.data,
                                                             rej.ctypes.data, status.ctypes.data))
-            node_y = np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N)
-            scale = V[:, None]
-        defect = y - node_y
-        return Propagation(y=y, defect=defect, relative_defect=defect / scale, accepted=acc, rejected=rej, segments=seg,
-                           status=status, ok=status == -1, terminal_defect=defect[:, -1], newton_rejected=nrej,
-                           newton_iterations=nit)
+        return Propagation(y=y, accepted=acc, rejected=rej, segments=seg, status=status, newton_rejected=nrej,
+                           newton_iterations=nit, **self._propagation_fields(phase, y, status, V, device))
 
     def propagate_dense(self, phase: int, t=None, *, tau=None, restart="nodes", rtol: float = 1e-9, atol=None,
                         integral_atol=None, substeps=None, max_steps: int = 4096):
@@ -1008,23 +1019,14 @@ class Solution:
         NumPy out, unless ``t`` / ``tau``, ``restart``, ``atol`` or ``integral_atol`` is a torch device tensor: then
         torch tensors on that device.  Bad arguments raise ``ValueError`` before anything is launched."""
         phase = self._phase(phase, need_handle=False)
-        pl, mesh = self.engine.layout.phases[phase], self.engine.meshes[phase]
+        pl = self.engine.layout.phases[phase]
         N, n_y, n_q = pl.N, pl.n_y, pl.n_q
-        device = next((a.device for a in (t, tau, restart, atol, integral_atol) if _is_torch(a) and a.is_cuda), None)
-        seg = propagation_segments(restart, mesh.s, N)
-        V = self.state_scale(phase)
-        if atol is None:
-            at = float(rtol) * V
-        else:
-            if _is_torch(atol):
-                atol = atol.detach().cpu().numpy()
-            at = np.ascontiguousarray(np.broadcast_to(np.asarray(atol, dtype=np.float64), (n_y,)))
-        check_propagate_tolerances(substeps, rtol, at, max_steps)
-        at = np.ascontiguousarray(at, dtype=np.float64)
+        seg, at, V, device, n_seg, m = self._propagate_prelude(phase, restart, rtol, atol, substeps, max_steps,
+                                                               (t, tau, restart, atol, integral_atol))
         ia = check_integral_atol(integral_atol, n_q)
         tq = dense_query_tau(t, tau, self.initial_time[phase], self.final_time[phase])
         self._phase(phase)     # (the device is needed from here on)
-        Q, n_seg, m = int(tq.shape[0]), len(seg) - 1, 0 if substeps is None else int(substeps)
+        Q = int(tq.shape[0])
         head = (self._h, phase, n_seg, seg.ctypes.data, m, float(rtol), at.ctypes.data if n_y else None,
                 ia.ctypes.data if (ia is not None and n_q) else None, int(max_steps), Q, tq.ctypes.data if Q else None)
         q_nlp = np.asarray(self.integral[phase], dtype=np.float64).reshape(n_q)
@@ -1039,8 +1041,6 @@ class Solution:
             self._check(self._lib.pc_solution_propagate_dense_device(*head, ptr(y), ptr(acc), ptr(rej), ptr(status), ptr(qa),
                                                                      ptr(yd), ptr(qd)))
             self._check(self._lib.pc_synchronize(self.engine._h))
-            node_y = torch.as_tensor(np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N), device=device)
-            scale = torch.as_tensor(V, device=device)[:, None]
             integral = torch.as_tensor(_sum_ascending(qa[:, torch.as_tensor(ends, device=device)].cpu().numpy()), device=device)
             q_nlp = torch.as_tensor(q_nlp, device=device)
             tq_where = torch.as_tensor(tq, device=device)
@@ -1050,15 +1050,12 @@ class Solution:
             ptr = lambda a: a.ctypes.data if a.size else None   # noqa: E731
             self._check(self._lib.pc_solution_propagate_dense(*head, ptr(y), ptr(acc), ptr(rej), ptr(status), ptr(qa), ptr(yd),
                                                               ptr(qd)))
-            node_y = np.asarray(self.state[phase], dtype=np.float64).reshape(n_y, N)
-            scale = V[:, None]
             integral = _sum_ascending(qa[:, ends])
             tq_where = tq
         if Q:
             u_dense = self.sample(phase, tau=tq_where)[2]
         else:
             u_dense = yd.new_empty((pl.n_u, 0)) if device is not None else np.empty((pl.n_u, 0))
-        defect = y - node_y
-        return DensePropagation(y=y, defect=defect, relative_defect=defect / scale, accepted=acc, rejected=rej, segments=seg,
-                                status=status, ok=status == -1, terminal_defect=defect[:, -1], q=qa, integral=integral,
-                                integral_defect=integral - q_nlp, tau=tq, y_dense=yd, q_dense=qd, u_dense=u_dense)
+        return DensePropagation(y=y, accepted=acc, rejected=rej, segments=seg, status=status, q=qa, integral=integral,
+                                integral_defect=integral - q_nlp, tau=tq, y_dense=yd, q_dense=qd, u_dense=u_dense,
+                                **self._propagation_fields(phase, y, status, V, device))
